@@ -2,8 +2,13 @@
 """bench.py -- rows/s + achieved HBM GB/s on the numbers_mt aggregation hot path
 (BASELINE.json metric), 1..8 GPUs of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--query c3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--query c3] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run sets up, settles, warms up, times K steps, writes the last step's
+outputs when --dump-outputs is given, and prints its line.  --full adds, after
+the timed steps, the legs beside the headline figure (one GPU): the CPU
+baseline, the C-host leg and the world-1 RCCL exchange leg.
 
 Workload (BASELINE.json configs[2], the north_star query):
   SELECT sum(number)/count(number), max(number), min(number)
@@ -157,6 +162,36 @@ def project_closed_form(b, e):
 def log(rank, *a):
     if rank == 0:
         print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_SAMPLE_ROWS = 4096  # --dump-outputs: rows sampled per column of an output left in HBM
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: name -> u64 values (a result row, a result column
+    or a sample of one), each written as DIR/<name>.npy in float64.  float64
+    rounds a u64 above 2^53, so the exact bits go beside it as two exact
+    float64 halves: <name>_hi32.npy and <name>_lo32.npy.  A NULL is 0."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.array([0 if v is None else int(v) % U64 for v in a], dtype=np.uint64) if isinstance(a, (list, tuple)) \
+            else np.ascontiguousarray(a).astype(np.uint64)
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
+        np.save(os.path.join(dirname, name + "_hi32.npy"), (a >> np.uint64(32)).astype(np.float64))
+        np.save(os.path.join(dirname, name + "_lo32.npy"), (a & np.uint64(0xFFFFFFFF)).astype(np.float64))
+
+
+def sample_rows(n, salt=0):
+    """DUMP_SAMPLE_ROWS sorted row indices in [0, n) (every row when n is
+    smaller), the same for the same (n, salt) in every run, as a cuda tensor."""
+    import numpy as np
+    if n <= DUMP_SAMPLE_ROWS:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng([DUMP_SEED, salt]).integers(0, n, DUMP_SAMPLE_ROWS, dtype=np.int64))
+    return torch.from_numpy(idx).cuda()
 
 
 def settle(step, seconds, world, backend):
@@ -428,6 +463,31 @@ def _device_block_sums(b):
     return out
 
 
+def _device_block_sample(b, salt):
+    """--dump-outputs: each column of one fq_device_block at sample_rows() of
+    its rows, as host int64 arrays.  Block-stream layout: sampled over the
+    whole geometry, a row past its block's count reads 0; plain columns:
+    sampled over the valid rows."""
+    n = b.columns[0].len if b.n_columns else 0
+    stream = b.block_rows > 0 and n
+    idx = sample_rows(n if stream else int(b.rows), salt)
+    valid = None
+    if stream:
+        counts = ops.device_view(b.d_counts, 8 * b.n_blocks).view(torch.int64)
+        valid = (idx % b.block_rows) < counts[idx // b.block_rows]
+    out = []
+    for j in range(b.n_columns):
+        c = b.columns[j]
+        if not c.len or not idx.numel():
+            out.append(torch.zeros(0, dtype=torch.int64).numpy())
+            continue
+        v = ops.device_view(c.data, 8 * c.len).view(torch.int64)[idx]
+        if valid is not None:
+            v = torch.where(valid, v, torch.zeros_like(v))
+        out.append(v.cpu().numpy())
+    return out
+
+
 def run_project_engine(args, rank, world, local):
     """--query p1, default path: FilterTransform -> ProjectionTransform through
     the ENGINE (fq_engine_execute_blocks): SQL -> PipelineBuilder -> Source x P
@@ -457,12 +517,17 @@ def run_project_engine(args, rank, world, local):
         len(mine), total_rows, total_rows * 8 / 1e9, rank))
     expect = _p1_expect(mine)
 
-    def step(check=False):
+    def step(check=False, sample=None):
+        # sample (--dump-outputs): (pipe, its n-th block) -> the block's sampled columns; the
+        # pipes' blocks interleave differently from run to run, a pipe's own order is fixed
         kept = s1 = s2 = 0
         blocks = 0
         with eng.execute_blocks(sql, rank, world) as st:
             for b in st:
                 blocks += 1
+                if sample is not None:
+                    seq = sum(1 for p, _ in sample if p == b.pipe)
+                    sample[(b.pipe, seq)] = _device_block_sample(b, b.pipe * 1000003 + seq)
                 if check:
                     k, x, y = _device_block_sums(b)
                     kept, s1, s2 = kept + k, (s1 + x) % U64, (s2 + y) % U64
@@ -501,9 +566,20 @@ def run_project_engine(args, rank, world, local):
     if bad:
         raise SystemExit("PARITY FAILURE: a timed step kept another row count")
     st = eng.stats()
-    got, _ = step(check=True)
+    # --dump-outputs: a timed step's blocks are gone once the host has pulled them (60 GB per
+    # query), so the sample is taken from the checked step below as its blocks pass: the same
+    # statement over the same resident column, its sums checked like every step's
+    sample = {} if args.dump_outputs and rank == 0 else None
+    got, _ = step(check=True, sample=sample)
     if got != expect:
         raise SystemExit("PARITY FAILURE after the timed steps: got %r expected %r" % (got, expect))
+    if sample is not None:
+        import numpy as np
+        order = sorted(sample)
+        arrays = {"kept_rows": [k]}  # the last timed step's own count
+        for j in range(len(sample[order[0]]) if order else 0):
+            arrays["column_%d_sample" % j] = np.concatenate([sample[key][j] for key in order])
+        dump_outputs(args.dump_outputs, arrays)
     launches = max(st["project_launches"], 1)
     avg_ms = st["project_ms"] / launches
     bytes_per_launch = st["project_bytes"] / launches
@@ -656,6 +732,22 @@ def run_project(args, rank, world):
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed launch's outputs, still in its output pair: kept rows, per-block counts
+        # (blocks path) and both columns at sample_rows() of the rows the launch defines
+        n_out = cols[-1].len if blocks else kept.value
+        idx = sample_rows(n_out)
+        arrays = {"kept_rows": [kept.value]}
+        if blocks:
+            cnt = counts.buf[:8 * (-(-n_out // BLOCK_SIZE))].view(torch.int64)
+            arrays["block_counts"] = cnt.cpu().numpy()
+            valid = (idx % BLOCK_SIZE) < cnt[idx // BLOCK_SIZE]  # rows past a block's count are not output
+        for j, o in enumerate(sets[(i - 1) % nsets]):
+            v = o.buf[:n_out * 8].view(torch.int64)[idx]
+            if blocks:
+                v = torch.where(valid, v, torch.zeros_like(v))
+            arrays["column_%d_sample" % j] = v.cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     if checked(cols[-1], 0) != expect[-1]:
         raise SystemExit("PARITY FAILURE after the timed steps")
     ms = [e0.elapsed_time(e1) for e0, e1, _, _ in evs]
@@ -943,11 +1035,20 @@ def main():
                     help="rows of the CPU-baseline sample (default: the whole 1e10-row workload, ~1.5 s on the "
                          "box's 8 threads for c3, ~5 s for p1; 4e9 rows for GROUP BY, a hash insert per row, ~3-10 s)")
     ap.add_argument("--cpu-threads", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline figure (one GPU only): the CPU "
+                         "baseline, the C-host leg and the world-1 RCCL exchange leg.  Without it a run sets up, "
+                         "settles, warms up, times --steps steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64, with "
+                         "exact <name>_hi32 / <name>_lo32 halves): the result row or the GROUP BY columns; for p1 a "
+                         "fixed seeded sample of the projected columns left in HBM (engine path: of the checked "
+                         "step after the timed ones, whose blocks can still be read)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-c-host", action="store_true",
-                    help="skip the C-host leg (fq_c_client --bench in a child process, c3 at N=1)")
+                    help="--full: skip the C-host leg (fq_c_client --bench in a child process, c3 at N=1)")
     ap.add_argument("--no-rccl-world1", action="store_true",
-                    help="skip the world-1 RCCL exchange leg (fq_engine_execute_rccl, aggregates at N=1)")
+                    help="--full: skip the world-1 RCCL exchange leg (fq_engine_execute_rccl, aggregates at N=1)")
     ap.add_argument("--project-path", default="engine", choices=("engine", "blocks", "contiguous"),
                     help="p1: through the engine (fq_engine_execute_blocks, default), or the kernel alone at the "
                          "C ABI: block-stream output (fq_filter_project_blocks) or one contiguous output per "
@@ -976,6 +1077,12 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch and rendezvous only (gloo, no GPU): rank 0 prints the ranks that arrived")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    # the legs beside the headline figure run under --full only
+    args.no_cpu_baseline |= not args.full
+    args.no_c_host |= not args.full
+    args.no_rccl_world1 |= not args.full
 
     if args.cpu_only:
         return cpu_only_line(args)
@@ -1174,6 +1281,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert same_result(res, expect)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result as its caller got it: the one row, or the GROUP BY columns
+        if one_row:
+            dump_outputs(args.dump_outputs, {"row": res})
+        else:
+            cols = res if world == 1 else [list(c) for c in zip(*res)]
+            dump_outputs(args.dump_outputs, {"column_%d" % c: v for c, v in enumerate(cols)})
 
     st = eng.stats()
     jit1 = ops.jit_stats()

@@ -164,6 +164,22 @@ def test_settle_runs_untimed_steps_for_about_the_requested_time():
     assert n == len(calls) and time.perf_counter() - t0 >= 0.15, (n, time.perf_counter() - t0)
 
 
+def test_dump_outputs_writes_float64_with_exact_halves(tmp_path):
+    # --dump-outputs: <name>.npy in float64 (rounded above 2^53), the u64 bits exact in _hi32 / _lo32
+    import numpy as np
+    b = _bench()
+    row = [2**64 - 1, 2**53 + 1, 0, None]
+    col = np.array([5, 2**63 + 3], dtype=np.uint64)
+    b.dump_outputs(str(tmp_path / "out"), {"row": row, "column_0": col})
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(n + s + ".npy" for n in ("row", "column_0")
+                                                          for s in ("", "_hi32", "_lo32"))
+    for name, want in (("row", [2**64 - 1, 2**53 + 1, 0, 0]), ("column_0", [5, 2**63 + 3])):
+        v, hi, lo = (np.load(tmp_path / "out" / (name + s + ".npy")) for s in ("", "_hi32", "_lo32"))
+        assert v.dtype == hi.dtype == lo.dtype == np.float64
+        assert [int(h) * 2**32 + int(l) for h, l in zip(hi, lo)] == want
+        assert list(v) == [float(x) for x in want]
+
+
 def test_kernel_gaps_busy_time_is_the_union_of_launch_intervals(tmp_path):
     # tools/kernel_gaps.py --window: the rocprof figure held beside bench.py's
     # span when launches on the two row queues overlap -- the time at least one

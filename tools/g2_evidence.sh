@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 R=$(pwd); OUT="$R/gpurun_out/g2e"; mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 300 python -u bench.py --query g2 --steps 10 --warmup 3 > "$OUT/bench_g2.json" 2> "$OUT/bench_g2.err"
+timeout -k 10 300 python -u bench.py --full --query g2 --steps 10 --warmup 3 > "$OUT/bench_g2.json" 2> "$OUT/bench_g2.err"
 rc=$?; echo "bench rc=$rc"; cat "$OUT/bench_g2.json"; [ $rc -eq 0 ] || exit $rc
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 "$R/bench.py" --query g2 --steps 5 --warmup 1 --no-cpu-baseline > "$OUT/prof.json" 2> "$OUT/prof.err"

@@ -655,7 +655,8 @@ DataValue fold_leaf(uint32_t op, const DataValue &a, const DataValue &b) {
     bool b_better;
     if (dt == FQ_DT_FLOAT64) {
         const double x = __builtin_bit_cast(double, a.bits), y = __builtin_bit_cast(double, b.bits);
-        b_better = op == FQ_AGG_MAX ? y > x : y < x;
+        // f64::max / f64::min, as the device tables fold: a NaN state is ignored unless both are NaN
+        b_better = (op == FQ_AGG_MAX ? y > x : y < x) || (x != x && y == y);
     } else if (dt == FQ_DT_INT64) {
         const int64_t x = (int64_t)a.bits, y = (int64_t)b.bits;
         b_better = op == FQ_AGG_MAX ? y > x : y < x;

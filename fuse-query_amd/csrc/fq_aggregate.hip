@@ -33,8 +33,8 @@ struct Acc {
     uint32_t flags;
     __device__ void init() {
         sum = V(0);
-        mx = Lim<V>::lo();
-        mn = Lim<V>::hi();
+        mx = MinMaxId<V>::max_id();
+        mn = MinMaxId<V>::min_id();
         cnt = 0;
         flags = 0;
     }

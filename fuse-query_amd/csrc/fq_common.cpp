@@ -143,8 +143,10 @@ fq_status fq_state_merge(const fq_agg_state *states, int32_t n, fq_agg_state *ou
             __builtin_memcpy(&mn_b, &s.min, 8);
             double sum = a + b;
             if (dt == FQ_DT_FLOAT32) sum = (double)((float)a + (float)b);
-            const double mx = mx_b > mx_a ? mx_b : mx_a;
-            const double mn = mn_b < mn_a ? mn_b : mn_a;
+            // f64::max / f64::min, as the engine's DataValue merge: a NaN state
+            // is ignored unless both are NaN
+            const double mx = (mx_b > mx_a || mx_a != mx_a) ? mx_b : mx_a;
+            const double mn = (mn_b < mn_a || mn_a != mn_a) ? mn_b : mn_a;
             __builtin_memcpy(&r.sum, &sum, 8);
             __builtin_memcpy(&r.max, &mx, 8);
             __builtin_memcpy(&r.min, &mn, 8);

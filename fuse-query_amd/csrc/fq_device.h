@@ -155,6 +155,30 @@ template <typename V>
 __device__ __forceinline__ V vmax(V a, V b) { return b > a ? b : a; }
 template <typename V>
 __device__ __forceinline__ V vmin(V a, V b) { return b < a ? b : a; }
+// Floats fold as Rust's f64::max / f64::min (the engine's DataValue merge):
+// a NaN is ignored unless every folded value is NaN.  The running value
+// starts at NaN (MinMaxId), so the first value of any kind replaces it.
+__device__ __forceinline__ double vmax(double a, double b) { return (b > a || a != a) ? b : a; }
+__device__ __forceinline__ double vmin(double a, double b) { return (b < a || a != a) ? b : a; }
+__device__ __forceinline__ float vmax(float a, float b) { return (b > a || a != a) ? b : a; }
+__device__ __forceinline__ float vmin(float a, float b) { return (b < a || a != a) ? b : a; }
+
+// identity of the max / min fold: the type's limits for integers, NaN for floats
+template <typename V>
+struct MinMaxId {
+    __device__ static constexpr V max_id() { return Lim<V>::lo(); }
+    __device__ static constexpr V min_id() { return Lim<V>::hi(); }
+};
+template <>
+struct MinMaxId<double> {
+    __device__ static constexpr double max_id() { return __builtin_nan(""); }
+    __device__ static constexpr double min_id() { return __builtin_nan(""); }
+};
+template <>
+struct MinMaxId<float> {
+    __device__ static constexpr float max_id() { return __builtin_nanf(""); }
+    __device__ static constexpr float min_id() { return __builtin_nanf(""); }
+};
 
 // ---------------------------------------------------------------------------
 // Column element -> step dtype (operand = FQ_OPERAND_COLUMN)
@@ -342,8 +366,8 @@ __device__ __forceinline__ void run_prog(const KProg &p, const TIn (&x)[E], uint
 }
 
 // a OP b for the generic divide/modulo codes; a zero divisor yields 0 (the
-// caller raises DIV_ZERO for live rows).  i64::MIN / -1 wraps (unpinned in
-// the reference).
+// caller raises DIV_ZERO for live rows).  i64::MIN / -1 wraps to i64::MIN and
+// x % -1 is 0, as the oracle states them (tests/test_edge_values_gpu.py).
 __device__ __noinline__ inline uint64_t slow_divmod(int32_t code, uint64_t a, uint64_t b) {
     switch (code) {
         case K_DIV_U:

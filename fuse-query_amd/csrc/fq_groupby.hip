@@ -14,7 +14,7 @@
 //   states[a][r][capacity + 1]  per aggregate a and replica r < R (see
 //                               group_replicas: workgroup b updates replica
 //                               b % R), initialised to the identity of its
-//                               kind (0, +max, lowest) so atomics need no
+//                               kind (0, +max, lowest; NaN for Float64 max/min) so atomics need no
 //                               occupancy check; extract folds the replicas
 // The accumulate kernel is generated per shape with hipRTC (fq_jit.hip
 // gen_groupby_source); init / count / extract are precompiled here.
@@ -47,7 +47,7 @@ static uint64_t identity_bits(int32_t kind, int32_t dt) {
     if (kind == FQ_AGG_COUNT || kind == FQ_AGG_SUM) return 0;
     if (dt == FQ_DT_UINT64) return kind == FQ_AGG_MAX ? 0ull : ~0ull;
     if (dt == FQ_DT_INT64) return kind == FQ_AGG_MAX ? 0x8000000000000000ull : 0x7fffffffffffffffull;
-    return kind == FQ_AGG_MAX ? 0xfff0000000000000ull : 0x7ff0000000000000ull;  // -inf / +inf
+    return 0x7ff8000000000000ull;  // Float64 max/min: NaN, replaced by the first non-NaN value
 }
 
 static fq_status view(const fq_group_table *t, TableView &v) {
@@ -100,8 +100,9 @@ __device__ __forceinline__ uint64_t fold(int32_t kind, int32_t dt, uint64_t x, u
     if (dt == FQ_DT_FLOAT64) {
         const double a = __builtin_bit_cast(double, x), b = __builtin_bit_cast(double, y);
         if (kind == FQ_AGG_SUM) return __builtin_bit_cast(uint64_t, a + b);
-        if (kind == FQ_AGG_MAX) return b > a ? y : x;
-        return b < a ? y : x;
+        // f64::max / f64::min: a NaN side is ignored unless both are NaN
+        if (kind == FQ_AGG_MAX) return (b > a || (a != a && b == b)) ? y : x;
+        return (b < a || (a != a && b == b)) ? y : x;
     }
     if (kind == FQ_AGG_SUM) return x + y;
     if (dt == FQ_DT_INT64) {

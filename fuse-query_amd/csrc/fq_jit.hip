@@ -461,6 +461,44 @@ template <typename T> __device__ __forceinline__ T vmax(T a, T b) { return b > a
 template <typename T> __device__ __forceinline__ T vmin(T a, T b) { return b < a ? b : a; }
 )";
 
+// Float64 max/min (fq_device.h): a NaN is ignored unless every folded value is
+// NaN; the running value starts at NaN.  Appended for shapes with a Float64
+// max/min only, so integer shapes keep their source.
+const char *kFloatMinMax = R"(
+__device__ __forceinline__ double vmax(double a, double b) { return (b > a || a != a) ? b : a; }
+__device__ __forceinline__ double vmin(double a, double b) { return (b < a || a != a) ? b : a; }
+)";
+
+// GROUP BY Float64 max/min states under the same rule: the state starts at
+// NaN, a value replaces a NaN state, a NaN value never replaces anything.
+// (The group-by source below still carries the older amax_f64 / amin_f64 and
+// their "NaN never wins" note, now unused: its text stays as it was so that
+// integer shapes generate the same source as before.)
+const char *kGroupFloatMinMax = R"(
+__device__ __forceinline__ void amax_f64n(u64 *p, double v) {
+    if (v != v) return;
+    u64 old = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        const double o = __builtin_bit_cast(double, old);
+        if (!(v > o || o != o)) return;
+        const u64 prev = atomicCAS((unsigned long long *)p, old, __builtin_bit_cast(u64, v));
+        if (prev == old) return;
+        old = prev;
+    }
+}
+__device__ __forceinline__ void amin_f64n(u64 *p, double v) {
+    if (v != v) return;
+    u64 old = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        const double o = __builtin_bit_cast(double, old);
+        if (!(v < o || o != o)) return;
+        const u64 prev = atomicCAS((unsigned long long *)p, old, __builtin_bit_cast(u64, v));
+        if (prev == old) return;
+        old = prev;
+    }
+}
+)";
+
 // Body of `bool fq_pred(TIn x, ...)`: the lowered predicate program on x,
 // then the comparison in cmp_dtype.
 bool emit_leaf(Gen &g, int32_t cmp, int32_t cmp_dtype, int32_t rhs_operand, const KProg &lhs, const std::string &rhs,
@@ -559,6 +597,7 @@ bool gen_source(const Launch &L, int32_t tin, bool chain, Gen &g, std::string &s
     emit_value_body(g, chain ? &L.val : nullptr, tin, L.vdtype, "v", "V", val_body);
 
     src = kCommon;
+    if (L.vdtype == FQ_DT_FLOAT64) src += kFloatMinMax;
     src += "typedef " + std::string(TIn) + " TIn;\ntypedef " + V + " V;\n";
     src += "struct Step { u64 c, m, s; };\nstruct Consts { u64 rhs; Step p[" + std::to_string(kSteps) +
            "], v[" + std::to_string(kSteps) + "]; u64 rl[" + std::to_string(FQ_MAX_PRED_LEAVES) + "]; Step pl[" +
@@ -586,7 +625,7 @@ bool gen_source(const Launch &L, int32_t tin, bool chain, Gen &g, std::string &s
     std::string lo, hi;
     if (L.vdtype == FQ_DT_UINT64) lo = "0ull", hi = "~0ull";
     else if (L.vdtype == FQ_DT_INT64) lo = "(-9223372036854775807ll - 1)", hi = "9223372036854775807ll";
-    else lo = "-__builtin_huge_val()", hi = "__builtin_huge_val()";
+    else lo = hi = "__builtin_nan(\"\")";  // MinMaxId<double>
 
     // reduce_and_store (fq_aggregate.hip): wave butterfly, LDS across the 4
     // waves; thread 0 returns the workgroup's Partial
@@ -900,10 +939,10 @@ std::string state_update(int32_t kind, int32_t dt, const std::string &P, const s
             if (dt == FQ_DT_FLOAT64) return "atomicAdd((double *)(" + P + "), " + v + ");";
             return "atomicAdd((unsigned long long *)(" + P + "), (unsigned long long)(" + v + "));";
         case FQ_AGG_MAX:
-            if (dt == FQ_DT_FLOAT64) return "amax_f64((u64 *)(" + P + "), " + v + ");";
+            if (dt == FQ_DT_FLOAT64) return "amax_f64n((u64 *)(" + P + "), " + v + ");";
             return std::string("atomicMax((") + T + " *)(" + P + "), (" + T + ")(" + v + "));";
         default:
-            if (dt == FQ_DT_FLOAT64) return "amin_f64((u64 *)(" + P + "), " + v + ");";
+            if (dt == FQ_DT_FLOAT64) return "amin_f64n((u64 *)(" + P + "), " + v + ");";
             return std::string("atomicMin((") + T + " *)(" + P + "), (" + T + ")(" + v + "));";
     }
 }
@@ -1521,6 +1560,13 @@ bool gen_groupby_source(const GroupLaunch &G, int32_t tin, Gen &g, std::string &
     const int NA = G.n_aggs;
     const int S = lds_slots(NA, G.lds_bytes);
     src = kCommon;
+    for (int a = 0; a < NA; ++a) {
+        if (G.dtypes[a] == FQ_DT_FLOAT64 && (G.kinds[a] == FQ_AGG_MAX || G.kinds[a] == FQ_AGG_MIN)) {
+            src += kFloatMinMax;
+            src += kGroupFloatMinMax;
+            break;
+        }
+    }
     src += "typedef " + std::string(TIn) + " TIn;\n";
     src += "struct Step { u64 c, m, s; };\nstruct Consts { u64 rhs; Step p[" + std::to_string(kSteps) + "], k[" +
            std::to_string(kSteps) + "], v[" + std::to_string(FQ_MAX_GROUP_AGGS) + "][" + std::to_string(kSteps) +
@@ -1670,7 +1716,7 @@ __device__ long long ginsert(const Tab &t, u64 k) {
         if (kind == FQ_AGG_COUNT || kind == FQ_AGG_SUM) return "0ull";
         if (dt == FQ_DT_UINT64) return kind == FQ_AGG_MAX ? "0ull" : "0xffffffffffffffffull";
         if (dt == FQ_DT_INT64) return kind == FQ_AGG_MAX ? "0x8000000000000000ull" : "0x7fffffffffffffffull";
-        return kind == FQ_AGG_MAX ? "0xfff0000000000000ull" : "0x7ff0000000000000ull";  // -inf / +inf
+        return "0x7ff8000000000000ull";  // Float64 max/min: NaN (kFloatMinMax)
     };
     // per-row work in two halves so a tile's 8 rows issue their first LDS
     // probe reads together (independent loads, one latency): fq_prep
@@ -2828,8 +2874,12 @@ fq_status compile(const std::string &src, int dev, Compiled &out, const char *fn
             stage = 1;
             return;
         }
-        const char *opts[] = {arch.c_str(), "-O3", "-std=c++17"};
-        if (r.compile(prog, 3, opts) != HIPRTC_SUCCESS) {
+        // -ffp-contract=off: the steps of a Float64 chain are emitted inline, and the
+        // default (fast) fuses `a * b` feeding `+` / `-` into one fma -- one rounding
+        // where the reference and the interpreting scan make two: 1 * 1e308 * 10.0 -
+        // inf gave -inf for inf - inf = NaN.  Integer shapes have no such pair.
+        const char *opts[] = {arch.c_str(), "-O3", "-std=c++17", "-ffp-contract=off"};
+        if (r.compile(prog, 4, opts) != HIPRTC_SUCCESS) {
             size_t n = 0;
             r.log_size(prog, &n);
             log.assign(n + 1, '\0');

@@ -201,8 +201,8 @@ typedef struct fq_pred {
 #define FQ_STATE_CAST_NULL 4u
 typedef struct fq_agg_state {
     uint64_t sum;   /* wrapping sum (integers) / binary64 sum bits (floats)      */
-    uint64_t max;
-    uint64_t min;
+    uint64_t max;    /* float dtypes: f64::max / f64::min folds -- a NaN row is ignored */
+    uint64_t min;    /* unless every kept row is NaN (then NaN, with count > 0)      */
     uint64_t count;  /* rows that passed the predicate                           */
     uint64_t blocks; /* reference blocks covered                                 */
     uint32_t flags;

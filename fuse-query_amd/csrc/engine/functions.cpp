@@ -13,8 +13,33 @@ static bool is_chain_dtype(DataType dt) {
     return dt == FQ_DT_UINT64 || dt == FQ_DT_INT64 || dt == FQ_DT_FLOAT64;
 }
 
+int FusedColumns::index(const std::string &name, DataType dt) {
+    for (size_t i = 0; i < names.size(); ++i)
+        if (names[i] == name) return (int)i;
+    if (names.size() >= FQ_MAX_SCAN_COLS) return -1;
+    names.push_back(name);
+    dtypes.push_back(dt);
+    return (int)names.size() - 1;
+}
+
+bool FusedChain::with_load(fq_expr &out) const {
+    out = expr;
+    if (start == 0) return true;
+    if (expr.n_steps >= FQ_MAX_STEPS) return false;
+    for (int i = expr.n_steps; i > 0; --i) out.steps[i] = out.steps[i - 1];
+    out.steps[0] = fq_step{};
+    out.steps[0].op = FQ_OP_LOAD;
+    out.steps[0].dtype = col_dtype;
+    out.steps[0].bits = (uint64_t)start;
+    out.n_steps = expr.n_steps + 1;
+    if (expr.n_steps == 0) out.out_dtype = col_dtype;
+    return true;
+}
+
 std::string FusedChain::key() const {
-    std::string k = column + ":" + std::to_string(col_dtype) + ":" + std::to_string(out_dtype);
+    std::string k;
+    for (const std::string &c : columns) k += c + ";";  // a scan over several columns: keyed by the list
+    k += column + ":" + std::to_string(col_dtype) + ":" + std::to_string(out_dtype);
     for (int i = 0; i < expr.n_steps; ++i) {
         const fq_step &s = expr.steps[i];
         k += "/" + std::to_string(s.op) + "," + std::to_string(s.operand) + "," + std::to_string(s.reversed) +
@@ -27,6 +52,7 @@ std::string FusedPred::key() const {
     auto leaf = [this](const fq_expr &lhs, int32_t cmp, int32_t cdt, int32_t ro, uint64_t rb) {
         FusedChain c;
         c.column = column;
+        c.columns = columns;
         c.col_dtype = col_dtype;
         c.expr = lhs;
         c.out_dtype = lhs.out_dtype;
@@ -135,7 +161,7 @@ void FieldFunction::merge_state(const std::vector<DataValue> &) {
 }
 DataValue FieldFunction::merge_result() const { throw_internal("Unsupported aggregate operation for function field"); }
 
-bool FieldFunction::to_chain(const DataSchema &s, FusedChain &c) const {
+bool FieldFunction::to_chain(const DataSchema &s, FusedChain &c, FusedColumns *cols) const {
     int idx;
     try {
         idx = s.index_of(name_);
@@ -145,6 +171,16 @@ bool FieldFunction::to_chain(const DataSchema &s, FusedChain &c) const {
     const DataType dt = s.fields[(size_t)idx].dtype;
     if (!dtype_is_numeric(dt)) return false;
     c = FusedChain{};
+    if (cols) {
+        // one column may be narrow (the interpreting scan reads it); with a
+        // second one in the list every column is 64-bit
+        const int k = cols->index(name_, dt);
+        if (k < 0) return false;
+        if (cols->names.size() > 1)
+            for (DataType d : cols->dtypes)
+                if (!is_chain_dtype(d)) return false;
+        c.start = k;
+    }
     c.column = name_;
     c.col_dtype = dt;
     c.expr.n_steps = 0;
@@ -204,10 +240,13 @@ static bool tree_fusion_enabled() {
 }
 
 // Append one step `acc OP operand` (or `operand OP acc`) to a chain.
-static bool push_step(FusedChain &c, int32_t op, bool column_operand, const DataValue *k, bool reversed) {
+// A column operand is `col` (an identity chain); null: the chain's own column.
+static bool push_step(FusedChain &c, int32_t op, bool column_operand, const DataValue *k, bool reversed,
+                      const FusedChain *col = nullptr) {
     if (c.expr.n_steps >= FQ_MAX_STEPS) return false;
     if (!is_chain_dtype(c.col_dtype)) return false;
-    const DataType odt = column_operand ? c.col_dtype : k->dtype;
+    if (col && !is_chain_dtype(col->col_dtype)) return false;
+    const DataType odt = column_operand ? (col ? col->col_dtype : c.col_dtype) : k->dtype;
     int32_t ct = 0;
     const int32_t l = reversed ? odt : c.out_dtype, r = reversed ? c.out_dtype : odt;
     if (fqc::numerical_coercion(fqc::arith_op_str(op), l, r, &ct) != FQ_OK) return false;
@@ -217,7 +256,7 @@ static bool push_step(FusedChain &c, int32_t op, bool column_operand, const Data
     st.operand = column_operand ? FQ_OPERAND_COLUMN : FQ_OPERAND_CONST;
     st.reversed = reversed ? 1 : 0;
     st.dtype = ct;
-    st.bits = 0;
+    st.bits = column_operand && col ? (uint64_t)col->start : 0;
     if (!column_operand && !fqc::cast_scalar(k->bits, k->dtype, ct, &st.bits)) return false;
     c.expr.n_steps++;
     c.expr.out_dtype = ct;
@@ -230,11 +269,12 @@ static bool numeric_constant(const Function &f, const DataValue *&v) {
     return v && v->kind == DataValue::kSome && dtype_is_numeric(v->dtype);
 }
 
-bool ArithmeticFunction::to_chain(const DataSchema &s, FusedChain &c) const {
+bool ArithmeticFunction::to_chain(const DataSchema &s, FusedChain &c, FusedColumns *cols) const {
     const DataValue *k = nullptr;
     const std::string *fld = nullptr;
-    FusedChain l, r;  // each child lowered once
-    const bool lok = left_->to_chain(s, l), rok = right_->to_chain(s, r);
+    FusedChain l, r;  // each child lowered once (left first: the columns' numbers follow first appearance)
+    const bool lok = left_->to_chain(s, l, cols);
+    const bool rok = right_->to_chain(s, r, cols);
     if (numeric_constant(*right_, k) && lok) {
         c = l;
         return push_step(c, op_, false, k, false);
@@ -243,21 +283,23 @@ bool ArithmeticFunction::to_chain(const DataSchema &s, FusedChain &c) const {
         c = r;
         return push_step(c, op_, false, k, true);
     }
-    if ((fld = right_->as_field()) && lok && *fld == l.column) {
+    if ((fld = right_->as_field()) && lok && (*fld == l.column || (cols && rok))) {
         c = l;
-        return push_step(c, op_, true, nullptr, false);
+        return push_step(c, op_, true, nullptr, false, cols ? &r : nullptr);
     }
-    if ((fld = left_->as_field()) && rok && *fld == r.column) {
+    if ((fld = left_->as_field()) && rok && (*fld == r.column || (cols && lok))) {
         c = r;
-        return push_step(c, op_, true, nullptr, true);
+        return push_step(c, op_, true, nullptr, true, cols ? &l : nullptr);
     }
     // both children are expressions over the same column: an expression tree
     // (left subtree, FQ_OP_PUSH, right subtree, then this node with the
     // popped left value as its operand) -- hipRTC kernels only
-    if (!lok || !rok || l.column != r.column || !tree_fusion_enabled()) return false;
+    // (with a column list the subtrees may start from different columns:
+    // FQ_OP_PUSH names the one the right subtree starts from)
+    if (!lok || !rok || (l.column != r.column && !cols) || !tree_fusion_enabled()) return false;
     if (l.expr.n_steps + r.expr.n_steps + 2 > FQ_MAX_STEPS) return false;
     const int depth = std::max(l.depth, 1 + r.depth);
-    if (depth > FQ_MAX_STACK || !is_chain_dtype(l.col_dtype)) return false;
+    if (depth > FQ_MAX_STACK || !is_chain_dtype(l.col_dtype) || !is_chain_dtype(r.col_dtype)) return false;
     int32_t ct = 0;
     if (fqc::numerical_coercion(fqc::arith_op_str(op_), l.out_dtype, r.out_dtype, &ct) != FQ_OK || !is_chain_dtype(ct))
         return false;
@@ -265,7 +307,8 @@ bool ArithmeticFunction::to_chain(const DataSchema &s, FusedChain &c) const {
     fq_step &push = c.expr.steps[c.expr.n_steps++];
     push = fq_step{};
     push.op = FQ_OP_PUSH;
-    push.dtype = l.col_dtype;
+    push.dtype = r.col_dtype;
+    push.bits = (uint64_t)r.start;
     for (int i = 0; i < r.expr.n_steps; ++i) c.expr.steps[c.expr.n_steps++] = r.expr.steps[i];
     fq_step &node = c.expr.steps[c.expr.n_steps++];
     node = fq_step{};
@@ -315,9 +358,12 @@ static int32_t flip(int32_t cmp) {
     }
 }
 
-static bool make_pred(const FusedChain &lhs, int32_t cmp, bool column_rhs, const DataValue *k, FusedPred &p) {
+// A column right-hand side is `col` (an identity chain); null: lhs's own column.
+static bool make_pred(const FusedChain &lhs, int32_t cmp, bool column_rhs, const DataValue *k, FusedPred &p,
+                      const FusedChain *col = nullptr) {
     if (!is_chain_dtype(lhs.col_dtype)) return false;
-    const DataType rdt = column_rhs ? lhs.col_dtype : k->dtype;
+    if (col && !is_chain_dtype(col->col_dtype)) return false;
+    const DataType rdt = column_rhs ? (col ? col->col_dtype : lhs.col_dtype) : k->dtype;
     int32_t ct = 0;
     if (fqc::equal_coercion(fqc::cmp_op_str(cmp), lhs.out_dtype, rdt, &ct) != FQ_OK) return false;
     if (!is_chain_dtype(ct)) return false;
@@ -328,18 +374,27 @@ static bool make_pred(const FusedChain &lhs, int32_t cmp, bool column_rhs, const
     p.pred.cmp = cmp;
     p.pred.cmp_dtype = ct;
     p.pred.rhs_operand = column_rhs ? FQ_OPERAND_COLUMN : FQ_OPERAND_CONST;
-    p.pred.lhs = lhs.expr;
+    if (!lhs.with_load(p.pred.lhs)) return false;
+    if (column_rhs && col) p.pred.rhs_bits = (uint64_t)col->start;
     if (!column_rhs && !fqc::cast_scalar(k->bits, k->dtype, ct, &p.pred.rhs_bits)) return false;
     return true;
 }
 
-bool ComparisonFunction::to_pred(const DataSchema &s, FusedPred &p) const {
+bool ComparisonFunction::to_pred(const DataSchema &s, FusedPred &p, FusedColumns *cols) const {
     const DataValue *k = nullptr;
     const std::string *fld = nullptr;
     FusedChain c;
-    if (numeric_constant(*right_, k) && left_->to_chain(s, c)) return make_pred(c, cmp_, false, k, p);
+    if (numeric_constant(*right_, k) && left_->to_chain(s, c, cols)) return make_pred(c, cmp_, false, k, p);
     // scalar-array form: the reference flips the operator (data_array_comparison.rs:76-84)
-    if (numeric_constant(*left_, k) && right_->to_chain(s, c)) return make_pred(c, flip(cmp_), false, k, p);
+    if (numeric_constant(*left_, k) && right_->to_chain(s, c, cols)) return make_pred(c, flip(cmp_), false, k, p);
+    if (cols) {  // any column on one side, an expression over the listed columns on the other
+        FusedChain f;
+        if (right_->as_field() && left_->to_chain(s, c, cols) && right_->to_chain(s, f, cols))
+            return make_pred(c, cmp_, true, nullptr, p, &f);
+        if (left_->as_field() && left_->to_chain(s, f, cols) && right_->to_chain(s, c, cols))
+            return make_pred(c, flip(cmp_), true, nullptr, p, &f);
+        return false;
+    }
     if ((fld = right_->as_field()) && left_->to_chain(s, c) && *fld == c.column) return make_pred(c, cmp_, true, nullptr, p);
     if ((fld = left_->as_field()) && right_->to_chain(s, c) && *fld == c.column)
         return make_pred(c, flip(cmp_), true, nullptr, p);
@@ -529,26 +584,27 @@ DataValue LogicFunction::merge_result() const {
 // An and/or tree of fusable comparisons over one column -> FQ_PRED_TREE
 // (postfix program over at most FQ_MAX_PRED_LEAVES leaves).
 static bool flatten_logic(const Function &f, const DataSchema &s, FusedPred &out, std::vector<FusedPred> &leaves,
-                          std::vector<int32_t> &prog) {
+                          std::vector<int32_t> &prog, FusedColumns *cols) {
     if (const auto *lf = dynamic_cast<const LogicFunction *>(&f)) {
-        if (!flatten_logic(lf->left(), s, out, leaves, prog) || !flatten_logic(lf->right(), s, out, leaves, prog))
+        if (!flatten_logic(lf->left(), s, out, leaves, prog, cols) ||
+            !flatten_logic(lf->right(), s, out, leaves, prog, cols))
             return false;
         prog.push_back(lf->op() == FQ_LOGIC_AND ? FQ_PRED_AND : FQ_PRED_OR);
         return true;
     }
     FusedPred p;
-    if (!f.to_pred(s, p) || p.pred.kind != FQ_PRED_EXPR) return false;
+    if (!f.to_pred(s, p, cols) || p.pred.kind != FQ_PRED_EXPR) return false;
     if (leaves.size() >= FQ_MAX_PRED_LEAVES) return false;
-    if (!leaves.empty() && p.column != leaves[0].column) return false;
+    if (!cols && !leaves.empty() && p.column != leaves[0].column) return false;
     prog.push_back((int32_t)leaves.size());
     leaves.push_back(p);
     return true;
 }
 
-bool LogicFunction::to_pred(const DataSchema &s, FusedPred &p) const {
+bool LogicFunction::to_pred(const DataSchema &s, FusedPred &p, FusedColumns *cols) const {
     std::vector<FusedPred> leaves;
     std::vector<int32_t> prog;
-    if (!flatten_logic(*this, s, p, leaves, prog) || leaves.empty()) return false;
+    if (!flatten_logic(*this, s, p, leaves, prog, cols) || leaves.empty()) return false;
     p = FusedPred{};
     p.column = leaves[0].column;
     p.col_dtype = leaves[0].col_dtype;
@@ -1098,8 +1154,20 @@ void AggFusion::add(AggregatorFunction *agg, const DataBlock &b) {
     const DataSchema &s = *b.schema;
     FusedChain fc;
     FusedPred fp;
-    bool ok = agg->arg().to_chain(s, fc);
-    if (ok && b.filter) ok = b.filter->to_pred(s, fp) && fp.column == fc.column;
+    // the scan's columns in order of first appearance: the filter's, then the
+    // argument's.  More than one: fq_aggregate_columns, which needs the
+    // hipRTC kernels and the FQ_OP_LOAD step to fit; a shape that does not fit
+    // (a fifth column, a ninth step, a deeper stack, the JIT off) takes the
+    // unfused branch below like any other unfusable shape.
+    FusedColumns cols;
+    bool ok = !b.filter || b.filter->to_pred(s, fp, &cols);
+    if (ok) ok = agg->arg().to_chain(s, fc, &cols);
+    fq_expr value_expr = fc.expr;
+    if (ok && cols.names.size() > 1) {
+        ok = tree_fusion_enabled() && fc.with_load(value_expr);
+        for (DataType d : cols.dtypes) ok = ok && is_chain_dtype(d);
+        fc.columns = fp.columns = cols.names;
+    }
     if (!ok) {
         Entry en;
         en.agg = agg;
@@ -1120,8 +1188,11 @@ void AggFusion::add(AggregatorFunction *agg, const DataBlock &b) {
         cur_.emplace_back();
         g = &cur_.back();
         g->key = key;
-        g->col = b.column_by_name(fc.column);
+        g->col = b.column_by_name(cols.names[0]);
+        if (cols.names.size() > 1)
+            for (const std::string &name : cols.names) g->cols.push_back(b.column_by_name(name));
         g->value = fc;
+        g->value_expr = value_expr;
         g->has_pred = (bool)b.filter;
         if (g->has_pred) g->pred = fp;
         g->filter_keepalive = b.filter;
@@ -1145,6 +1216,9 @@ void AggFusion::end_block() {
     const bool pairs = prof == 1 || (prof == 2 && !(ticket_ && ticket_->group()));
     for (Group &g : cur_) {
         fq_col c = g.col.abi();
+        fq_col cs[FQ_MAX_SCAN_COLS];
+        const int32_t n_cols = (int32_t)g.cols.size();  // 0: one column, fq_aggregate
+        for (int32_t j = 0; j < n_cols; ++j) cs[j] = g.cols[(size_t)j].abi();
         void *dst = nullptr;
         check_hip(hipHostGetDevicePointer(&dst, slot_host(g.slot), 0), "hipHostGetDevicePointer");
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1152,7 +1226,10 @@ void AggFusion::end_block() {
             e0 = ctx_.res->take_event();
             e1 = ctx_.res->take_event();
         }
-        if (prof && (g.has_pred || g.value.expr.n_steps)) {
+        if (prof && n_cols) {
+            check_fq(fq_jit_prepare_columns(cs, n_cols, g.block_rows, g.has_pred ? g.pred.get() : nullptr,
+                                            g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask, nullptr));
+        } else if (prof && (g.has_pred || g.value.expr.n_steps)) {
             // compile a specialised scan (first use of this expression shape)
             // outside the timed region (identity scans are precompiled)
             fq_jit_stats js;
@@ -1169,8 +1246,13 @@ void AggFusion::end_block() {
             const fq_expr *val = g.value.expr.n_steps ? &g.value.expr : nullptr;
             if (ticket_ && ticket_->group()) ticket_->group()->before_launch(ctx_);
             if (pairs) check_hip(hipEventRecord(e0, stream_), "hipEventRecord");
-            check_fq(fq_aggregate(&c, g.block_rows, pred, val, g.mask, (fq_agg_state *)dst, res_->ws, res_->ws_bytes,
-                                  stream_));
+            if (n_cols)
+                check_fq(fq_aggregate_columns(cs, n_cols, g.block_rows, pred,
+                                              g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask,
+                                              (fq_agg_state *)dst, res_->ws, res_->ws_bytes, stream_));
+            else
+                check_fq(fq_aggregate(&c, g.block_rows, pred, val, g.mask, (fq_agg_state *)dst, res_->ws,
+                                      res_->ws_bytes, stream_));
             if (pairs) check_hip(hipEventRecord(e1, stream_), "hipEventRecord");
         }
         launched_ = true;
@@ -1179,12 +1261,16 @@ void AggFusion::end_block() {
         if (pairs) events_.push_back({e0, e1});
         ctx_.rt->stats.scan_launches++;
         ctx_.rt->stats.scan_rows += (uint64_t)g.col.len;
-        ctx_.rt->stats.scan_bytes += (uint64_t)g.col.len * (uint64_t)dtype_size(g.col.dtype);
+        // every column of the scan is read once: 8 x columns x rows over several
+        ctx_.rt->stats.scan_bytes +=
+            (uint64_t)g.col.len * (uint64_t)dtype_size(g.col.dtype) * (uint64_t)(n_cols ? n_cols : 1);
         // a stream-ordered column (hipFreeAsync on the queue the scan was just
         // enqueued on) may be dropped now: its memory returns to the pool only
         // after the scan -- so a query over generated chunks holds one chunk per
         // pipe, not all of them; a synchronously allocated one is kept to finish()
         if (g.col.dev && !g.col.dev->async) keepalive_.push_back(g.col);
+        for (const Column &gc : g.cols)
+            if (gc.dev && !gc.dev->async) keepalive_.push_back(gc);
     }
     cur_.clear();
 }

@@ -14,14 +14,33 @@
 
 namespace fq {
 
-// An ArithmeticFunction tree expressed as fq_expr over one column.
+// The columns one fused scan reads (fq_aggregate_columns), numbered in order
+// of first appearance: the block's filter first, then the argument.  A caller
+// that passes one to to_pred / to_chain accepts shapes over up to
+// FQ_MAX_SCAN_COLS 64-bit columns; without one the hooks keep to one column.
+struct FusedColumns {
+    std::vector<std::string> names;
+    std::vector<DataType> dtypes;
+    // the column's number (a new one if it has none yet); -1: no room left
+    int index(const std::string &name, DataType dt);
+};
+
+// An ArithmeticFunction tree expressed as fq_expr over one column, or, with a
+// FusedColumns list, over several: `column` is then the column the expression
+// starts from, number `start` of the list, and the steps carry the numbers of
+// the others (fq_gpu.h, fq_aggregate_columns).
 struct FusedChain {
     std::string column;
     DataType col_dtype = FQ_DT_NULL;
     fq_expr expr{};
     DataType out_dtype = FQ_DT_NULL;
     int depth = 0;  // value-stack depth the expression tree needs (FQ_OP_PUSH)
+    int start = 0;  // the number of `column` in the list
+    std::vector<std::string> columns;  // the scan's column list (AggFusion fills it in)
     std::string key() const;
+    // the expression as fq_aggregate_columns takes it: FQ_OP_LOAD in front when
+    // it starts from another column than 0; false: no step left for it
+    bool with_load(fq_expr &out) const;
 };
 
 // A ComparisonFunction (or an and/or tree of them, FQ_PRED_TREE) expressed
@@ -31,6 +50,7 @@ struct FusedPred {
     DataType col_dtype = FQ_DT_NULL;
     fq_pred pred{};
     fq_pred_tree tree{};  // kind == FQ_PRED_TREE
+    std::vector<std::string> columns;  // the scan's column list (AggFusion fills it in)
     std::string key() const;
     // the fq_pred to hand to the ABI (points pred.tree at this object's tree)
     const fq_pred *get() {
@@ -58,8 +78,8 @@ class Function {
     virtual FunctionRef clone() const = 0;
 
     // fusion hooks (not in the reference: describe the shape, no semantics)
-    virtual bool to_chain(const DataSchema &, FusedChain &) const { return false; }
-    virtual bool to_pred(const DataSchema &, FusedPred &) const { return false; }
+    virtual bool to_chain(const DataSchema &, FusedChain &, FusedColumns * = nullptr) const { return false; }
+    virtual bool to_pred(const DataSchema &, FusedPred &, FusedColumns * = nullptr) const { return false; }
     virtual const DataValue *as_constant() const { return nullptr; }
     virtual const std::string *as_field() const { return nullptr; }
     // the AggregatorFunction leaves of this tree, left to right (GROUP BY
@@ -81,7 +101,7 @@ class FieldFunction : public Function {
     void merge_state(const std::vector<DataValue> &) override;
     DataValue merge_result() const override;
     FunctionRef clone() const override { return std::make_shared<FieldFunction>(*this); }
-    bool to_chain(const DataSchema &s, FusedChain &c) const override;
+    bool to_chain(const DataSchema &s, FusedChain &c, FusedColumns *cols = nullptr) const override;
     const std::string *as_field() const override { return &name_; }
 
    private:
@@ -123,8 +143,12 @@ class AliasFunction : public Function {
     void merge_state(const std::vector<DataValue> &s) override { func_->merge_state(s); }
     DataValue merge_result() const override { return func_->merge_result(); }
     FunctionRef clone() const override { return std::make_shared<AliasFunction>(alias_, func_->clone()); }
-    bool to_chain(const DataSchema &s, FusedChain &c) const override { return func_->to_chain(s, c); }
-    bool to_pred(const DataSchema &s, FusedPred &p) const override { return func_->to_pred(s, p); }
+    bool to_chain(const DataSchema &s, FusedChain &c, FusedColumns *cols = nullptr) const override {
+        return func_->to_chain(s, c, cols);
+    }
+    bool to_pred(const DataSchema &s, FusedPred &p, FusedColumns *cols = nullptr) const override {
+        return func_->to_pred(s, p, cols);
+    }
     void collect_aggregators(std::vector<AggregatorFunction *> &v) override { func_->collect_aggregators(v); }
 
    private:
@@ -161,7 +185,7 @@ class ArithmeticFunction : public Function {
         f->depth_ = depth_;
         return f;
     }
-    bool to_chain(const DataSchema &s, FusedChain &c) const override;
+    bool to_chain(const DataSchema &s, FusedChain &c, FusedColumns *cols = nullptr) const override;
     void collect_aggregators(std::vector<AggregatorFunction *> &v) override {
         left_->collect_aggregators(v);
         right_->collect_aggregators(v);
@@ -194,7 +218,7 @@ class ComparisonFunction : public Function {
         f->depth_ = depth_;
         return f;
     }
-    bool to_pred(const DataSchema &s, FusedPred &p) const override;
+    bool to_pred(const DataSchema &s, FusedPred &p, FusedColumns *cols = nullptr) const override;
     void collect_aggregators(std::vector<AggregatorFunction *> &v) override {
         left_->collect_aggregators(v);
         right_->collect_aggregators(v);
@@ -231,7 +255,7 @@ class LogicFunction : public Function {
         left_->collect_aggregators(v);
         right_->collect_aggregators(v);
     }
-    bool to_pred(const DataSchema &s, FusedPred &p) const override;
+    bool to_pred(const DataSchema &s, FusedPred &p, FusedColumns *cols = nullptr) const override;
     int32_t op() const { return op_; }
     const Function &left() const { return *left_; }
     const Function &right() const { return *right_; }
@@ -428,6 +452,8 @@ class AggFusion {
     struct Group {
         std::string key;
         Column col;
+        std::vector<Column> cols;  // more than one column: fq_aggregate_columns
+        fq_expr value_expr{};      // value.expr, FQ_OP_LOAD in front when it starts from another column than 0
         FusedChain value;
         bool has_pred = false;
         FusedPred pred;

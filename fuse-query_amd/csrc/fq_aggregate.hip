@@ -406,8 +406,13 @@ static fq_status push_cast(int32_t from, int32_t to, KProg &out) {
 }
 
 // fq_expr (semantic) -> KProg (lowered).  Returns the resulting dtype.
-fq_status lower_expr(const fq_expr &e, int32_t col_dtype, KProg &out, int32_t &res_dtype) {
+// n_cols == 0: the single-column entry points, which ignore the column indices
+// (every reference is the one column, of dtype cdt[0]).
+static fq_status lower_expr_impl(const fq_expr &e, const int32_t *cdt, int n_cols, KProg &out, int32_t &res_dtype) {
     out.n = 0;
+    const int32_t col_dtype = cdt[0];
+    // the column a step's `bits` names (-1: out of range)
+    auto col_of = [n_cols](uint64_t bits) -> int { return n_cols == 0 ? 0 : (bits < (uint64_t)n_cols ? (int)bits : -1); };
     int32_t acc = col_dtype;
     if (e.n_steps < 0 || e.n_steps > FQ_MAX_STEPS)
         return fqc::fail(FQ_E_INVALID, "fq_expr: n_steps out of range");
@@ -418,17 +423,32 @@ fq_status lower_expr(const fq_expr &e, int32_t col_dtype, KProg &out, int32_t &r
     int depth = 0;
     for (int i = 0; i < e.n_steps; ++i) {
         const fq_step &st = e.steps[i];
+        if (st.op == FQ_OP_LOAD && n_cols > 0) {  // the expression starts as another column than 0
+            if (i != 0) return fqc::fail(FQ_E_INVALID, "fq_step: FQ_OP_LOAD is the first step only");
+            const int c = col_of(st.bits);
+            if (c < 0) return fqc::fail(FQ_E_INVALID, "fq_step: column index out of range");
+            KStep &k = out.s[out.n++];
+            k = KStep{};
+            k.code = K_LOAD;
+            k.dtype = cdt[c];
+            k.col = c;
+            acc = cdt[c];
+            continue;
+        }
         if (st.op == FQ_OP_PUSH) {  // expression tree: acc onto the stack, restart from the column
             if (depth >= FQ_MAX_STACK) return fqc::fail(FQ_E_UNSUPPORTED, "expression tree too deep for the fused device path");
             if (!is_chain_dtype(col_dtype)) return fqc::fail(FQ_E_UNSUPPORTED, "fused expression trees need a 64-bit column");
             if (out.n >= (int)(sizeof(out.s) / sizeof(out.s[0])))
                 return fqc::fail(FQ_E_UNSUPPORTED, "expression too long for the fused device path");
+            const int c = col_of(st.bits);
+            if (c < 0) return fqc::fail(FQ_E_INVALID, "fq_step: column index out of range");
             KStep &k = out.s[out.n++];
             k = KStep{};
             k.code = K_PUSH;
-            k.dtype = col_dtype;
+            k.dtype = cdt[c];
+            k.col = c;
             stack[depth++] = acc;
-            acc = col_dtype;
+            acc = cdt[c];
             continue;
         }
         if (!is_chain_dtype(st.dtype))
@@ -446,8 +466,15 @@ fq_status lower_expr(const fq_expr &e, int32_t col_dtype, KProg &out, int32_t &r
         }
         fq_status s = push_cast(acc, st.dtype, out);
         if (s != FQ_OK) return s;
-        if (st.operand == FQ_OPERAND_COLUMN && col_dtype == FQ_DT_FLOAT64 && st.dtype != FQ_DT_FLOAT64)
-            return fqc::fail(FQ_E_INVALID, "fq_step: Float64 column operand in an integer step");
+        int ocol = 0;
+        if (st.operand == FQ_OPERAND_COLUMN) {
+            ocol = col_of(st.bits);
+            if (ocol < 0) return fqc::fail(FQ_E_INVALID, "fq_step: column index out of range");
+            if (cdt[ocol] == FQ_DT_FLOAT64 && st.dtype != FQ_DT_FLOAT64)
+                return fqc::fail(FQ_E_INVALID, "fq_step: Float64 column operand in an integer step");
+            if (n_cols > 0 && cdt[ocol] == FQ_DT_INT64 && st.dtype == FQ_DT_UINT64)
+                return fqc::fail(FQ_E_INVALID, "fq_step: Int64 column operand in a UInt64 step");
+        }
         if (out.n >= (int)(sizeof(out.s) / sizeof(out.s[0])))
             return fqc::fail(FQ_E_UNSUPPORTED, "expression too long for the fused device path");
         KStep &k = out.s[out.n++];
@@ -456,6 +483,7 @@ fq_status lower_expr(const fq_expr &e, int32_t col_dtype, KProg &out, int32_t &r
         k.reversed = st.reversed;
         k.dtype = st.dtype;
         k.sdtype = sdt;
+        k.col = ocol;
         k.c = st.bits;
         const bool konst = st.operand == FQ_OPERAND_CONST && !st.reversed;
         if (st.dtype == FQ_DT_FLOAT64) {
@@ -523,21 +551,45 @@ fq_status lower_expr(const fq_expr &e, int32_t col_dtype, KProg &out, int32_t &r
     return FQ_OK;
 }
 
+fq_status lower_expr(const fq_expr &e, int32_t col_dtype, KProg &out, int32_t &res_dtype) {
+    return lower_expr_impl(e, &col_dtype, 0, out, res_dtype);
+}
+
+fq_status lower_expr_cols(const fq_expr &e, const int32_t *cdt, int n_cols, KProg &out, int32_t &res_dtype) {
+    return lower_expr_impl(e, cdt, n_cols, out, res_dtype);
+}
+
 // fq_pred (semantic) -> KPred (lowered): predicate program cast to the
 // comparison type.
-fq_status lower_pred(const fq_pred *pred, int32_t col_dtype, int64_t len, bool need_data, KPred &out) {
+static fq_status lower_pred_impl(const fq_pred *pred, const int32_t *cdt, int n_cols, int64_t len, bool need_data,
+                                 KPred &out) {
     out = KPred{};
     out.kind = pred ? pred->kind : FQ_PRED_NONE;
+    const int32_t col_dtype = cdt[0];
+    // the right-hand column of a comparison in cmp_dtype: its index in *rc
+    auto rhs_col = [cdt, n_cols](int32_t rhs_operand, uint64_t bits, int32_t cmp_dtype, int32_t *rc) -> fq_status {
+        *rc = 0;
+        if (rhs_operand != FQ_OPERAND_COLUMN) return FQ_OK;
+        if (n_cols > 0) {
+            if (bits >= (uint64_t)n_cols) return fqc::fail(FQ_E_INVALID, "fq_pred: column index out of range");
+            *rc = (int32_t)bits;
+        }
+        if (cdt[*rc] == FQ_DT_FLOAT64 && cmp_dtype != FQ_DT_FLOAT64)
+            return fqc::fail(FQ_E_INVALID, "fq_pred: Float64 column compared as integer");
+        if (n_cols > 0 && cdt[*rc] == FQ_DT_INT64 && cmp_dtype == FQ_DT_UINT64)
+            return fqc::fail(FQ_E_INVALID, "fq_pred: Int64 column compared as UInt64");
+        return FQ_OK;
+    };
     if (out.kind == FQ_PRED_EXPR) {
         int32_t ldt = col_dtype;
-        fq_status s = lower_expr(pred->lhs, col_dtype, out.lhs, ldt);
+        fq_status s = lower_expr_impl(pred->lhs, cdt, n_cols, out.lhs, ldt);
         if (s != FQ_OK) return s;
         if (!is_chain_dtype(pred->cmp_dtype))
             return fqc::fail(FQ_E_UNSUPPORTED, "fused comparison type must be UInt64, Int64 or Float64");
         s = push_cast(ldt, pred->cmp_dtype, out.lhs);
         if (s != FQ_OK) return s;
-        if (pred->rhs_operand == FQ_OPERAND_COLUMN && col_dtype == FQ_DT_FLOAT64 && pred->cmp_dtype != FQ_DT_FLOAT64)
-            return fqc::fail(FQ_E_INVALID, "fq_pred: Float64 column compared as integer");
+        s = rhs_col(pred->rhs_operand, pred->rhs_bits, pred->cmp_dtype, &out.rhs_col);
+        if (s != FQ_OK) return s;
         out.cmp = pred->cmp;
         out.cmp_dtype = pred->cmp_dtype;
         out.rhs_operand = pred->rhs_operand;
@@ -559,15 +611,15 @@ fq_status lower_pred(const fq_pred *pred, int32_t col_dtype, int64_t len, bool n
             const fq_pred_leaf &lf = t->leaves[i];
             KLeaf &k = out.leaves[i];
             int32_t ldt = col_dtype;
-            fq_status s = lower_expr(lf.lhs, col_dtype, k.lhs, ldt);
+            fq_status s = lower_expr_impl(lf.lhs, cdt, n_cols, k.lhs, ldt);
             if (s != FQ_OK) return s;
             if (!is_chain_dtype(lf.cmp_dtype))
                 return fqc::fail(FQ_E_UNSUPPORTED, "fused comparison type must be UInt64, Int64 or Float64");
             s = push_cast(ldt, lf.cmp_dtype, k.lhs);
             if (s != FQ_OK) return s;
             if (lf.cmp < FQ_CMP_EQ || lf.cmp > FQ_CMP_GTEQ) return fqc::fail(FQ_E_INVALID, "fq_pred_leaf: bad cmp");
-            if (lf.rhs_operand == FQ_OPERAND_COLUMN && col_dtype == FQ_DT_FLOAT64 && lf.cmp_dtype != FQ_DT_FLOAT64)
-                return fqc::fail(FQ_E_INVALID, "fq_pred: Float64 column compared as integer");
+            s = rhs_col(lf.rhs_operand, lf.rhs_bits, lf.cmp_dtype, &k.rhs_col);
+            if (s != FQ_OK) return s;
             k.cmp = lf.cmp;
             k.cmp_dtype = lf.cmp_dtype;
             k.rhs_operand = lf.rhs_operand;
@@ -599,6 +651,15 @@ fq_status lower_pred(const fq_pred *pred, int32_t col_dtype, int64_t len, bool n
         return fqc::fail(FQ_E_INVALID, "fq_pred: bad kind");
     }
     return FQ_OK;
+}
+
+fq_status lower_pred(const fq_pred *pred, int32_t col_dtype, int64_t len, bool need_data, KPred &out) {
+    return lower_pred_impl(pred, &col_dtype, 0, len, need_data, out);
+}
+
+fq_status lower_pred_cols(const fq_pred *pred, const int32_t *cdt, int n_cols, int64_t len, bool need_data,
+                          KPred &out) {
+    return lower_pred_impl(pred, cdt, n_cols, len, need_data, out);
 }
 
 template <typename TIn, typename V, int PRED, bool CHAIN>
@@ -780,6 +841,101 @@ static fq_status plan_scan(const fq_col *col, int64_t block_rows, const fq_pred 
     return FQ_OK;
 }
 
+// The same for fq_aggregate_columns / fq_jit_prepare_columns over n_cols >= 2
+// checked columns (one column goes through plan_scan).
+static fq_status plan_scan_cols(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                const fq_expr *value, uint32_t agg_mask, bool need_data, Launch &L, bool &chain,
+                                uint64_t &blocks, int &empty_if_zero) {
+    const int64_t len = cols[0].len;
+    if (block_rows <= 0) block_rows = len > 0 ? len : 1;
+    L = Launch{};
+    L.col = cols[0].data;
+    L.n = len;
+    L.block_rows = block_rows;
+    L.mask = agg_mask;
+    L.n_cols = n_cols;
+    for (int j = 0; j < n_cols; ++j) {
+        L.cols[j] = cols[j].data;
+        L.cdt[j] = cols[j].dtype;
+    }
+    chain = value && value->n_steps > 0;
+    int32_t vdt = L.cdt[0];
+    if (chain) {
+        fq_status s = lower_expr_cols(*value, L.cdt, n_cols, L.val, vdt);
+        if (s != FQ_OK) return s;
+    }
+    L.vdtype = vdt;
+    fq_status ps = lower_pred_cols(pred, L.cdt, n_cols, len, need_data, L.pred);
+    if (ps != FQ_OK) return ps;
+
+    blocks = len == 0 ? 0 : (uint64_t)((len + block_rows - 1) / block_rows);
+    L.block_mode = L.pred.kind != FQ_PRED_NONE && (agg_mask & FQ_AGG_SUM) && blocks > 1;
+    empty_if_zero = (L.pred.kind != FQ_PRED_NONE && blocks == 1) ? 1 : 0;
+
+    // 16-byte loads need the same rows of every column on a 16-byte boundary
+    bool same_phase = true, aligned = true;
+    for (int j = 0; j < n_cols; ++j) {
+        same_phase = same_phase && ((((uintptr_t)cols[j].data) ^ ((uintptr_t)cols[0].data)) & 15u) == 0;
+        aligned = aligned && (((uintptr_t)cols[j].data) & 15u) == 0;
+    }
+    const int cus = fqc::device_cu_count();
+    const int max_grid = cus * 8 < kMaxPartials ? cus * 8 : kMaxPartials;
+    if (L.block_mode) {
+        int64_t grid = ((int64_t)blocks + (kThreads / kWave) - 1) / (kThreads / kWave);
+        L.grid = (int)(grid < max_grid ? (grid < 1 ? 1 : grid) : max_grid);
+        L.head = 0;
+        L.vec = aligned && (block_rows & 1) == 0;
+    } else {
+        L.vec = same_phase;
+        int64_t head = (((uintptr_t)cols[0].data) & 15u) ? 1 : 0;
+        if (head > len) head = len;
+        L.head = L.vec ? head : 0;
+        // a tile: scan_cols_vectors(n_cols) 16-byte vectors of every column per lane
+        const int64_t tile_rows = (int64_t)kThreads * scan_cols_vectors(n_cols) * 2;
+        int64_t grid = (len + tile_rows - 1) / tile_rows;
+        if (grid < 1) grid = 1;
+        const int64_t flat_max = (int64_t)cus * scan_wg_per_cu();
+        L.grid = (int)(grid < flat_max ? grid : flat_max);
+    }
+    return FQ_OK;
+}
+
+// argument checks of the two *_columns entry points
+static fq_status check_cols(const fq_col *cols, int32_t n_cols, bool need_data) {
+    if (!cols) return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: NULL argument");
+    if (n_cols < 1 || n_cols > FQ_MAX_SCAN_COLS)
+        return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: n_cols must be 1.." + std::to_string(FQ_MAX_SCAN_COLS) +
+                                           ", got " + std::to_string(n_cols));
+    for (int j = 0; j < n_cols; ++j) {
+        if (cols[j].len < 0) return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: negative length");
+        if (cols[j].len != cols[0].len)
+            return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: column " + std::to_string(j) + " has " +
+                                               std::to_string(cols[j].len) + " rows, column 0 has " +
+                                               std::to_string(cols[0].len));
+        if (!is_chain_dtype(cols[j].dtype))
+            return fqc::fail(FQ_E_UNSUPPORTED, std::string("fq_aggregate_columns: ") + fqc::dtype_name(cols[j].dtype) +
+                                                   " column (scans over several columns need UInt64, Int64 or "
+                                                   "Float64 columns)");
+        if (need_data && cols[j].len > 0 && !cols[j].data)
+            return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: NULL column data");
+        if (((uintptr_t)cols[j].data) % 8)
+            return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: column not aligned to its element size");
+    }
+    return FQ_OK;
+}
+
+// the column indices of a one-column program (all must be 0)
+static fq_status check_one_col(const fq_col *col, const fq_pred *pred, const fq_expr *value) {
+    KProg kp;
+    KPred kd;
+    int32_t dt = col->dtype;
+    if (value && value->n_steps > 0) {
+        fq_status s = lower_expr_cols(*value, &col->dtype, 1, kp, dt);
+        if (s != FQ_OK) return s;
+    }
+    return lower_pred_cols(pred, &col->dtype, 1, col->len, false, kd);
+}
+
 // fq_aggregate: the scan, then the fold of its partials, both on `stream`
 static fq_status aggregate(const fq_col *col, int64_t block_rows, const fq_pred *pred, const fq_expr *value,
                            uint32_t agg_mask, fq_agg_state *d_out, void *d_ws, size_t ws_bytes, hipStream_t stream) {
@@ -814,9 +970,79 @@ static fq_status aggregate(const fq_col *col, int64_t block_rows, const fq_pred 
     return dispatch_finalize(L, blocks, empty_if_zero, d_out);
 }
 
+// fq_aggregate_columns over two or more columns: hipRTC kernels only
+static fq_status aggregate_cols(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                const fq_expr *value, uint32_t agg_mask, fq_agg_state *d_out, void *d_ws,
+                                size_t ws_bytes, hipStream_t stream) {
+    if (!d_out || !d_ws) return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: NULL argument");
+    if (ws_bytes < kPartialsBytes) return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: workspace too small");
+    if (agg_mask & ~(uint32_t)(FQ_AGG_MIN | FQ_AGG_MAX | FQ_AGG_SUM | FQ_AGG_COUNT))
+        return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: unknown bits in agg_mask");
+    Launch L;
+    bool chain = false;
+    uint64_t blocks = 0;
+    int empty_if_zero = 0;
+    fq_status s = plan_scan_cols(cols, n_cols, block_rows, pred, value, agg_mask, true, L, chain, blocks, empty_if_zero);
+    if (s != FQ_OK) return s;
+    L.stream = stream;
+    L.parts = (Partial *)d_ws;
+    if (agg_mask == FQ_AGG_COUNT && !chain && L.pred.kind == FQ_PRED_NONE) {
+        L.grid = 0;  // count(column): rows, not values (see launch_finalize)
+        return dispatch_finalize(L, blocks, empty_if_zero, d_out);
+    }
+    bool jitted = false;
+    s = jit_scan(cols[0].dtype, chain, L, &jitted, true);
+    if (s != FQ_OK) return s;
+    if (!jitted)
+        return fqc::fail(FQ_E_UNSUPPORTED, "scans over several columns run on the hipRTC kernels only (FQ_JIT is off "
+                                           "or hipRTC is unavailable)");
+    return dispatch_finalize(L, blocks, empty_if_zero, d_out);
+}
+
 }  // namespace fqk
 
 extern "C" {
+
+fq_status fq_aggregate_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                               const fq_expr *value, uint32_t agg_mask, fq_agg_state *d_out, void *d_ws,
+                               size_t ws_bytes, void *stream) {
+    fq_status s = fqk::check_cols(cols, n_cols, true);
+    if (s != FQ_OK) return s;
+    if (n_cols == 1) {
+        s = fqk::check_one_col(cols, pred, value);
+        if (s != FQ_OK) return s;
+        return fqk::aggregate(cols, block_rows, pred, value, agg_mask, d_out, d_ws, ws_bytes, (hipStream_t)stream);
+    }
+    return fqk::aggregate_cols(cols, n_cols, block_rows, pred, value, agg_mask, d_out, d_ws, ws_bytes,
+                               (hipStream_t)stream);
+}
+
+fq_status fq_jit_prepare_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                 const fq_expr *value, uint32_t agg_mask, int32_t *specialised) {
+    using namespace fqk;
+    if (specialised) *specialised = 0;
+    fq_status s = check_cols(cols, n_cols, false);
+    if (s != FQ_OK) return s;
+    if (n_cols == 1) {
+        s = check_one_col(cols, pred, value);
+        if (s != FQ_OK) return s;
+        return fq_jit_prepare(cols, block_rows, pred, value, agg_mask, specialised);
+    }
+    Launch L;
+    bool chain = false;
+    uint64_t blocks = 0;
+    int empty_if_zero = 0;
+    s = plan_scan_cols(cols, n_cols, block_rows, pred, value, agg_mask, false, L, chain, blocks, empty_if_zero);
+    if (s != FQ_OK) return s;
+    bool ok = false;
+    s = jit_prepare(cols[0].dtype, chain, L, &ok);
+    if (s != FQ_OK) return s;
+    if (!ok)
+        return fqc::fail(FQ_E_UNSUPPORTED, "scans over several columns run on the hipRTC kernels only (FQ_JIT is off "
+                                           "or hipRTC is unavailable)");
+    if (specialised) *specialised = 1;
+    return FQ_OK;
+}
 
 fq_status fq_aggregate(const fq_col *col, int64_t block_rows, const fq_pred *pred, const fq_expr *value,
                        uint32_t agg_mask, fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream) {

@@ -45,6 +45,7 @@ enum Code : int32_t {
                  // and reduced once more -- 32-bit multiplies instead of a 64-bit mul-high
     K_DIVM32_U,  // u64 '/' by a constant d <= 65535: long division in 32/16/16-bit digits,
                  // each step a 32-bit magic divide (every partial dividend < d * 2^16)
+    K_LOAD,      // scans over several columns: acc = column `col` (hipRTC kernels only)
 };
 
 struct KStep {
@@ -57,7 +58,7 @@ struct KStep {
     uint32_t shift;
     uint32_t add;    // libdivide "add" marker
     int32_t sdtype;  // FQ_OPERAND_STACK: dtype of the popped value (cast to `dtype`)
-    int32_t pad;
+    int32_t col;     // scans over several columns: the column of FQ_OPERAND_COLUMN / K_PUSH / K_LOAD
 };
 
 struct KProg {
@@ -71,7 +72,7 @@ struct KLeaf {
     int32_t cmp;
     int32_t cmp_dtype;
     int32_t rhs_operand;
-    int32_t pad;
+    int32_t rhs_col;  // scans over several columns: the column of an FQ_OPERAND_COLUMN rhs
     uint64_t rhs;
     KProg lhs;
 };
@@ -92,6 +93,8 @@ struct KPred {
     int32_t n_prog;
     int32_t prog[2 * FQ_MAX_PRED_LEAVES];
     KLeaf leaves[FQ_MAX_PRED_LEAVES];
+    int32_t rhs_col;  // FQ_PRED_EXPR over several columns: the column of an FQ_OPERAND_COLUMN rhs
+    int32_t pad;
 };
 
 // Per-workgroup partial; same field order as fq_agg_state.

@@ -200,9 +200,9 @@ const char *ctype(int32_t dt) {
 }
 
 // column element x (type tin) -> 64-bit value encoding
-std::string x_bits(int32_t tin) {
-    if (tin == FQ_DT_FLOAT64) return "__builtin_bit_cast(u64, x)";
-    return "(u64)x";
+std::string x_bits(int32_t tin, const std::string &x = "x") {
+    if (tin == FQ_DT_FLOAT64) return "__builtin_bit_cast(u64, " + x + ")";
+    return "(u64)" + x;
 }
 
 // Constants of step i of the predicate ("p") or argument ("v") program are
@@ -237,6 +237,12 @@ struct Gen {
     std::string K(const char *field) const {
         return std::string("c.") + prefix + "[" + std::to_string(step) + "]." + field;
     }
+    // scans over several columns (fq_aggregate_columns): the row's elements are
+    // x0 .. x{n_cols-1} with dtypes cdt; otherwise the one element is x (tin)
+    int n_cols = 0;
+    int32_t cdt[FQ_MAX_SCAN_COLS] = {};
+    std::string X(int col) const { return n_cols > 1 ? "x" + std::to_string(col) : std::string("x"); }
+    int32_t xdt(int32_t tin, int col) const { return n_cols > 1 ? cdt[col] : tin; }
 };
 
 void pack_consts(const Launch &L, HostConsts &hc) {
@@ -310,16 +316,32 @@ std::string shape_key(const Launch &L, int32_t tin, bool chain, int dev) {
         }
     };
     if (chain) prog(L.val);
+    if (L.n_cols > 1) {  // scans over several columns: their dtypes and every column reference
+        put(L.n_cols);
+        put(scan_cols_vectors(L.n_cols));
+        for (int j = 0; j < L.n_cols; ++j) put(L.cdt[j]);
+        auto cols = [&put](const KProg &p) {
+            for (int i = 0; i < p.n; ++i) put(p.s[i].col);
+        };
+        if (chain) cols(L.val);
+        put(L.pred.rhs_col);
+        cols(L.pred.lhs);
+        for (int l = 0; l < L.pred.n_leaves; ++l) {
+            put(L.pred.leaves[l].rhs_col);
+            cols(L.pred.leaves[l].lhs);
+        }
+    }
     return k;
 }
 
 // col_as(dtype, x, live): the column as the operand of a step in `dt`
-std::string col_as(Gen &g, std::string &body, int32_t tin, int32_t dt) {
-    if (dt == FQ_DT_FLOAT64) return "__builtin_bit_cast(u64, (double)x)";
-    if (tin == FQ_DT_UINT64 && dt == FQ_DT_INT64)
-        body += "    flags |= (u32)((x >> 63) & (u64)live) * " + std::to_string(FQ_STATE_CAST_NULL) + "u;\n";
-    (void)g;
-    return x_bits(tin);
+std::string col_as(Gen &g, std::string &body, int32_t tin, int32_t dt, int col = 0) {
+    const std::string x = g.X(col);
+    const int32_t xt = g.xdt(tin, col);
+    if (dt == FQ_DT_FLOAT64) return "__builtin_bit_cast(u64, (double)" + x + ")";
+    if (xt == FQ_DT_UINT64 && dt == FQ_DT_INT64)
+        body += "    flags |= (u32)((" + x + " >> 63) & (u64)live) * " + std::to_string(FQ_STATE_CAST_NULL) + "u;\n";
+    return x_bits(xt, x);
 }
 
 // Straight-line code for one lowered program acting on `a`.
@@ -338,10 +360,11 @@ void emit_prog(Gen &g, std::string &body, const KProg &p, int32_t tin, const cha
             case K_CAST_I2F: body += "    a = __builtin_bit_cast(u64, (double)(long long)a);\n"; continue;
             case K_PUSH: {  // expression tree: keep acc, restart from the column
                 const std::string v = "s" + std::to_string(g.uid++);
-                body += "    const u64 " + v + " = a;\n    a = " + x_bits(tin) + ";\n";
+                body += "    const u64 " + v + " = a;\n    a = " + x_bits(g.xdt(tin, st.col), g.X(st.col)) + ";\n";
                 g.stk.push_back(v);
                 continue;
             }
+            case K_LOAD: body += "    a = " + x_bits(g.xdt(tin, st.col), g.X(st.col)) + ";\n"; continue;
             case K_SHR_U: body += "    a = a >> (u32)" + g.K("s") + ";\n"; continue;
             case K_AND_U: body += "    a = a & " + g.K("m") + ";\n"; continue;
             case K_MODM32_U: {
@@ -380,7 +403,7 @@ void emit_prog(Gen &g, std::string &body, const KProg &p, int32_t tin, const cha
         // binary step with an operand b
         std::string b;
         if (st.operand == FQ_OPERAND_COLUMN) {
-            b = col_as(g, body, tin, st.dtype);
+            b = col_as(g, body, tin, st.dtype, st.col);
         } else if (st.operand == FQ_OPERAND_STACK) {  // the left subtree's value, cast like acc
             const std::string v = g.stk.empty() ? std::string("0ull") : g.stk.back();
             if (!g.stk.empty()) g.stk.pop_back();
@@ -502,13 +525,13 @@ __device__ __forceinline__ void amin_f64n(u64 *p, double v) {
 // Body of `bool fq_pred(TIn x, ...)`: the lowered predicate program on x,
 // then the comparison in cmp_dtype.
 bool emit_leaf(Gen &g, int32_t cmp, int32_t cmp_dtype, int32_t rhs_operand, const KProg &lhs, const std::string &rhs,
-               const char *prefix, int32_t tin, std::string &body, const std::string &result) {
+               const char *prefix, int32_t tin, std::string &body, const std::string &result, int rhs_col = 0) {
     const char *op = cmp_op(cmp);
     if (!op) return false;
-    body += "    {\n    u64 a = " + x_bits(tin) + ";\n";
+    body += "    {\n    u64 a = " + x_bits(g.xdt(tin, 0), g.X(0)) + ";\n";
     emit_prog(g, body, lhs, tin, prefix);
     std::string r;
-    if (rhs_operand == FQ_OPERAND_COLUMN) r = col_as(g, body, tin, cmp_dtype);
+    if (rhs_operand == FQ_OPERAND_COLUMN) r = col_as(g, body, tin, cmp_dtype, rhs_col);
     else r = rhs;
     body += "    const u64 r = " + r + ";\n";
     if (cmp_dtype == FQ_DT_UINT64) body += "    " + result + " = a " + op + " r;\n";
@@ -531,7 +554,7 @@ bool emit_pred_body(Gen &g, const KPred &pr, int32_t tin, std::string &body) {
             body += "    bool " + b + ";\n";
             const std::string prefix = "pl[" + std::to_string(l) + "]";
             if (!emit_leaf(g, pr.leaves[l].cmp, pr.leaves[l].cmp_dtype, pr.leaves[l].rhs_operand, pr.leaves[l].lhs,
-                           "c.rl[" + std::to_string(l) + "]", prefix.c_str(), tin, body, b))
+                           "c.rl[" + std::to_string(l) + "]", prefix.c_str(), tin, body, b, pr.leaves[l].rhs_col))
                 return false;
         }
         std::vector<std::string> st;
@@ -554,10 +577,10 @@ bool emit_pred_body(Gen &g, const KPred &pr, int32_t tin, std::string &body) {
     }
     const char *op = cmp_op(pr.cmp);
     if (!op) return false;
-    body += "    u64 a = " + x_bits(tin) + ";\n";
+    body += "    u64 a = " + x_bits(g.xdt(tin, 0), g.X(0)) + ";\n";
     emit_prog(g, body, pr.lhs, tin, "p");
     std::string r;
-    if (pr.rhs_operand == FQ_OPERAND_COLUMN) r = col_as(g, body, tin, pr.cmp_dtype);
+    if (pr.rhs_operand == FQ_OPERAND_COLUMN) r = col_as(g, body, tin, pr.cmp_dtype, pr.rhs_col);
     else r = "c.rhs";
     body += "    const u64 r = " + r + ";\n";
     if (pr.cmp_dtype == FQ_DT_UINT64) body += std::string("    return a ") + op + " r;\n";
@@ -574,13 +597,129 @@ bool emit_pred_body(Gen &g, const KPred &pr, int32_t tin, std::string &body) {
 void emit_value_body(Gen &g, const KProg *prog, int32_t tin, int32_t vdt, const char *prefix, const char *vname,
                      std::string &body) {
     if (!prog) {
-        body += std::string("    return (") + vname + ")x;\n";
+        body += std::string("    return (") + vname + ")" + g.X(0) + ";\n";
         return;
     }
-    body += "    u64 a = " + x_bits(tin) + ";\n";
+    body += "    u64 a = " + x_bits(g.xdt(tin, 0), g.X(0)) + ";\n";
     emit_prog(g, body, *prog, tin, prefix);
     if (vdt == FQ_DT_FLOAT64) body += "    return __builtin_bit_cast(double, a);\n";
     else body += std::string("    return (") + vname + ")a;\n";
+}
+
+// The streaming loops of a scan over K >= 2 columns (fq_aggregate_columns):
+// the single-column loops below with the same rows of every column loaded
+// together.  `head` < 0 (the columns do not share a 16-byte phase, or block
+// mode with an odd block size): every column is read 8 bytes at a time, so
+// row i of one column always meets row i of the others.
+void gen_cols_loop(const Launch &L, int K, std::string &src) {
+    // FOR("text with @ for the column number") -> the text once per column
+    auto FOR = [K](const std::string &t, const char *sep = "") {
+        std::string o;
+        for (int j = 0; j < K; ++j) {
+            std::string u = t;
+            for (size_t p = 0; (p = u.find('@', p)) != std::string::npos;) u.replace(p, 1, std::to_string(j));
+            o += (j ? sep : "") + u;
+        }
+        return o;
+    };
+    const std::string CU = std::to_string(scan_cols_vectors(K));  // 16-byte vectors per lane per column in a tile
+    const std::string S8 = std::to_string(std::max(1, 8 / K));     // 8-byte loads per lane per column in flight
+    if (!L.block_mode) {
+        src += "\n    (void)R;\n"
+               "    const long long T = (long long)gridDim.x * 256;\n"
+               "    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;\n"
+               "    if (head >= 0) {\n"
+               "    const long long nvec = (n - head) / 2;\n";
+        src += FOR("    const u32x4 *__restrict__ vp@ = (const u32x4 *)(col@ + head);\n");
+        src += "    const long long TV = " + CU + " * 256;\n"
+               "    const long long ntiles = nvec / TV;\n"
+               "    // next tile's loads in flight while this tile is evaluated\n";
+        src += FOR("    u32x4 nxt@[" + CU + "];\n");
+        src += "    if ((long long)blockIdx.x < ntiles) {\n#pragma unroll\n"
+               "        for (int k = 0; k < " + CU + "; ++k) {\n"
+               "            const long long v = (long long)blockIdx.x * TV + threadIdx.x + (long long)k * 256;\n";
+        src += FOR("            nxt@[k] = __builtin_nontemporal_load(vp@ + v);\n");
+        src += "        }\n    }\n"
+               "    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {\n"
+               "        const long long base = t * TV + threadIdx.x;\n";
+        src += FOR("        u32x4 raw@[" + CU + "];\n");
+        src += "#pragma unroll\n        for (int k = 0; k < " + CU + "; ++k) { " + FOR("raw@[k] = nxt@[k]; ") + "}\n"
+               "        const long long tn = t + gridDim.x;\n"
+               "        if (tn < ntiles) {\n#pragma unroll\n"
+               "            for (int k = 0; k < " + CU + "; ++k) {\n"
+               "                const long long v = tn * TV + threadIdx.x + (long long)k * 256;\n";
+        src += FOR("                nxt@[k] = __builtin_nontemporal_load(vp@ + v);\n");
+        src += "            }\n        }\n#pragma unroll\n"
+               "        for (int k = 0; k < " + CU + "; ++k) {\n";
+        src += FOR("            TIn@ y@[2];\n            __builtin_memcpy(&y@[0], &raw@[k], 16);\n");
+        src += "            const long long i0 = head + (base + (long long)k * 256) * 2;\n"
+               "            fq_acc(acc, " + FOR("y@[0]", ", ") + ", i0, 1u, c, bitmap);\n"
+               "            fq_acc(acc, " + FOR("y@[1]", ", ") + ", i0 + 1, 1u, c, bitmap);\n"
+               "        }\n    }\n"
+               "    for (long long v = ntiles * TV + g; v < nvec; v += T) {\n";
+        src += FOR("        const u32x4 raw@ = __builtin_nontemporal_load(vp@ + v);\n"
+                   "        TIn@ y@[2];\n        __builtin_memcpy(&y@[0], &raw@, 16);\n");
+        src += "        fq_acc(acc, " + FOR("y@[0]", ", ") + ", head + v * 2, 1u, c, bitmap);\n"
+               "        fq_acc(acc, " + FOR("y@[1]", ", ") + ", head + v * 2 + 1, 1u, c, bitmap);\n"
+               "    }\n"
+               "    const long long tail0 = head + nvec * 2;\n"
+               "    const long long nedge = head + (n - tail0);\n"
+               "    for (long long t = g; t < nedge; t += T) {\n"
+               "        const long long i = t < head ? t : tail0 + (t - head);\n"
+               "        fq_acc(acc, " + FOR("col@[i]", ", ") + ", i, 1u, c, bitmap);\n"
+               "    }\n"
+               "    } else {\n"
+               "    for (long long i = g; i < n; i += T * " + S8 + ") {\n";
+        src += FOR("        TIn@ y@[" + S8 + "];\n");
+        src += "#pragma unroll\n        for (int k = 0; k < " + S8 + "; ++k) {\n"
+               "            const long long ik = i + (long long)k * T;\n";
+        src += FOR("            y@[k] = ik < n ? __builtin_nontemporal_load(col@ + ik) : TIn@(0);\n");
+        src += "        }\n#pragma unroll\n        for (int k = 0; k < " + S8 + "; ++k) {\n"
+               "            const long long ik = i + (long long)k * T;\n"
+               "            fq_acc(acc, " + FOR("y@[k]", ", ") + ", ik, ik < n ? 1u : 0u, c, bitmap);\n"
+               "        }\n    }\n    }\n";
+        return;
+    }
+    // block mode: one wave per reference block, the per-block empty ballot
+    src += "\n    const int lane = threadIdx.x & 63;\n"
+           "    const long long w = ((long long)blockIdx.x * 256 + threadIdx.x) / 64;\n"
+           "    const long long W = ((long long)gridDim.x * 256) / 64;\n"
+           "    const long long nb = (n + R - 1) / R;\n"
+           "    const bool vec = head >= 0;\n"
+           "    for (long long b = w; b < nb; b += W) {\n"
+           "        const long long s = b * R;\n"
+           "        const long long e = (s + R < n) ? s + R : n;\n"
+           "        u32 any = 0;\n"
+           "        if (vec) {\n"
+           "            const long long nv = (e - s) >> 1;\n";
+    src += FOR("            const u32x4 *__restrict__ bp@ = (const u32x4 *)(col@ + s);\n");
+    src += "            for (long long v = lane; v < nv; v += 64 * BM_U) {\n";
+    src += FOR("                u32x4 raw@[BM_U];\n");
+    src += "#pragma unroll\n                for (int k = 0; k < BM_U; ++k) {\n"
+           "                    const long long vk = v + (long long)k * 64;\n"
+           "                    if (vk < nv) { " + FOR("raw@[k] = __builtin_nontemporal_load(bp@ + vk); ") + "}\n"
+           "                    else { " + FOR("raw@[k] = u32x4{0u, 0u, 0u, 0u}; ") + "}\n"
+           "                }\n#pragma unroll\n                for (int k = 0; k < BM_U; ++k) {\n"
+           "                    const long long vk = v + (long long)k * 64;\n"
+           "                    const u32 li = vk < nv ? 1u : 0u;\n";
+    src += FOR("                    TIn@ y@[2];\n                    __builtin_memcpy(&y@[0], &raw@[k], 16);\n");
+    src += "                    any |= fq_acc(acc, " + FOR("y@[0]", ", ") + ", s + 2 * vk, li, c, bitmap);\n"
+           "                    any |= fq_acc(acc, " + FOR("y@[1]", ", ") + ", s + 2 * vk + 1, li, c, bitmap);\n"
+           "                }\n            }\n"
+           "            if (((e - s) & 1) && lane == 0) any |= fq_acc(acc, " + FOR("col@[e - 1]", ", ") + ", e - 1, 1u, c, bitmap);\n"
+           "            if (__ballot(any != 0) == 0ull) acc.flags |= " + std::to_string(FQ_STATE_ANY_EMPTY) + "u;\n"
+           "            continue;\n        }\n"
+           "        for (long long i = s + lane; i < e; i += 64 * " + S8 + ") {\n";
+    src += FOR("            TIn@ y@[" + S8 + "];\n");
+    src += "#pragma unroll\n            for (int k = 0; k < " + S8 + "; ++k) {\n"
+           "                const long long ik = i + (long long)k * 64;\n";
+    src += FOR("                y@[k] = ik < e ? __builtin_nontemporal_load(col@ + ik) : TIn@(0);\n");
+    src += "            }\n#pragma unroll\n            for (int k = 0; k < " + S8 + "; ++k) {\n"
+           "                const long long ik = i + (long long)k * 64;\n"
+           "                any |= fq_acc(acc, " + FOR("y@[k]", ", ") + ", ik, ik < e ? 1u : 0u, c, bitmap);\n"
+           "            }\n        }\n"
+           "        if (__ballot(any != 0) == 0ull) acc.flags |= " + std::to_string(FQ_STATE_ANY_EMPTY) + "u;\n"
+           "    }\n";
 }
 
 // Full kernel source for one shape.  Returns false if the shape is outside
@@ -590,6 +729,20 @@ bool gen_source(const Launch &L, int32_t tin, bool chain, Gen &g, std::string &s
     const char *V = ctype(L.vdtype);
     if (!TIn || !V) return false;
     const int32_t pk = L.pred.kind;
+    // scans over several columns: every per-row function takes x0 .. x{K-1}
+    const int K = L.n_cols > 1 ? L.n_cols : 0;
+    std::string XP = "TIn x", XA = "x";  // the row's elements as parameters / as arguments
+    if (K) {
+        g.n_cols = K;
+        XP = XA = "";
+        for (int j = 0; j < K; ++j) {
+            if (!ctype(L.cdt[j])) return false;
+            g.cdt[j] = L.cdt[j];
+            const std::string J = std::to_string(j);
+            XP += (j ? ", TIn" : "TIn") + J + " x" + J;
+            XA += (j ? ", x" : "x") + J;
+        }
+    }
 
     std::string pred_body, val_body;
     const bool expr_pred = pk == FQ_PRED_EXPR || pk == FQ_PRED_TREE;
@@ -598,24 +751,31 @@ bool gen_source(const Launch &L, int32_t tin, bool chain, Gen &g, std::string &s
 
     src = kCommon;
     if (L.vdtype == FQ_DT_FLOAT64) src += kFloatMinMax;
-    src += "typedef " + std::string(TIn) + " TIn;\ntypedef " + V + " V;\n";
+    if (K) {
+        for (int j = 0; j < K; ++j) src += "typedef " + std::string(ctype(L.cdt[j])) + " TIn" + std::to_string(j) + ";\n";
+        src += "typedef " + std::string(V) + " V;\n";
+    } else {
+        src += "typedef " + std::string(TIn) + " TIn;\ntypedef " + V + " V;\n";
+    }
     src += "struct Step { u64 c, m, s; };\nstruct Consts { u64 rhs; Step p[" + std::to_string(kSteps) +
            "], v[" + std::to_string(kSteps) + "]; u64 rl[" + std::to_string(FQ_MAX_PRED_LEAVES) + "]; Step pl[" +
            std::to_string(FQ_MAX_PRED_LEAVES) + "][" + std::to_string(kSteps) + "]; };\n";
-    src += "__device__ __forceinline__ bool fq_pred(TIn x, const Consts &c, u32 &flags, u32 live) {\n";
+    src += "__device__ __forceinline__ bool fq_pred(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n";
     src += expr_pred ? pred_body : "    return true;\n";
     src += "}\n";
-    src += "__device__ __forceinline__ V fq_val(TIn x, const Consts &c, u32 &flags, u32 live) {\n" + val_body + "}\n";
+    src += "__device__ __forceinline__ V fq_val(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n" + val_body + "}\n";
     const uint32_t m = L.mask;
-    src += "#define BM_U " + std::to_string(block_mode_vectors()) + "\n";
+    // block mode over K columns: the single-column kernel's loads in flight, shared
+    const int bm_u = K ? std::max(1, block_mode_vectors() / K) : block_mode_vectors();
+    src += "#define BM_U " + std::to_string(bm_u) + "\n";
     src += "struct Acc { V sum, mx, mn; u64 cnt; u32 flags; };\n";
-    src += "__device__ __forceinline__ u32 fq_acc(Acc &acc, TIn x, long long idx, u32 live, const Consts &c,\n"
+    src += "__device__ __forceinline__ u32 fq_acc(Acc &acc, " + XP + ", long long idx, u32 live, const Consts &c,\n"
            "                                      const u64 *__restrict__ bitmap) {\n"
            "    u32 pass = live;\n";
-    if (expr_pred) src += "    pass &= fq_pred(x, c, acc.flags, live) ? 1u : 0u;\n";
+    if (expr_pred) src += "    pass &= fq_pred(" + XA + ", c, acc.flags, live) ? 1u : 0u;\n";
     else if (pk == FQ_PRED_BITMAP)
         src += "    if (live) pass &= (u32)((bitmap[idx >> 6] >> (idx & 63)) & 1ull);\n";
-    src += "    (void)idx; (void)bitmap;\n    const V v = fq_val(x, c, acc.flags, pass);\n";
+    src += "    (void)idx; (void)bitmap;\n    const V v = fq_val(" + XA + ", c, acc.flags, pass);\n";
     if (m & FQ_AGG_SUM) src += "    acc.sum = acc.sum + (pass ? v : V(0));\n";
     if (m & FQ_AGG_MAX) src += "    acc.mx = pass ? vmax(acc.mx, v) : acc.mx;\n";
     if (m & FQ_AGG_MIN) src += "    acc.mn = pass ? vmin(acc.mn, v) : acc.mn;\n";
@@ -664,11 +824,19 @@ __device__ __forceinline__ Partial wg_reduce(Acc acc) {
     return p;
 }
 )";
+    std::string cols_params = "const TIn *__restrict__ col";
+    if (K) {
+        cols_params = "";
+        for (int j = 0; j < K; ++j)
+            cols_params += (j ? ", const TIn" : "const TIn") + std::to_string(j) + " *__restrict__ col" + std::to_string(j);
+    }
     src += "extern \"C\" __global__ void __launch_bounds__(256)\n"
-           "fq_jit_scan(const TIn *__restrict__ col, long long n, long long head, long long R,\n"
+           "fq_jit_scan(" + cols_params + ", long long n, long long head, long long R,\n"
            "            const u64 *__restrict__ bitmap, Consts c, Partial *parts) {\n"
            "    Acc acc;\n    acc.sum = V(0); acc.mx = " + lo + "; acc.mn = " + hi + "; acc.cnt = 0; acc.flags = 0;\n";
-    if (!L.block_mode) {
+    if (K) {
+        gen_cols_loop(L, K, src);
+    } else if (!L.block_mode) {
         // flat tile-contiguous streaming (agg_flat_kernel, U = 4 16-byte vectors per lane)
         src += R"(
     (void)R;
@@ -2920,6 +3088,7 @@ void jit_count_interp() { g_interp_launches += 1; }
 namespace {
 
 bool eligible(int32_t col_dtype, bool chain, const Launch &L) {
+    if (L.n_cols > 1) return true;  // scans over several columns have no other kernel
     if (!chain && L.pred.kind == FQ_PRED_NONE) return false;  // identity scans are already specialised
     return fqc::dtype_size(col_dtype) == 8;                      // expressions are 64-bit; narrow columns interpret
 }
@@ -2997,6 +3166,26 @@ fq_status jit_scan(int32_t col_dtype, bool chain, const Launch &L, bool *used, b
     long long n = L.n, head = L.head, R = L.block_rows;
     const uint64_t *bitmap = L.pred.bitmap;
     Partial *parts = L.parts;
+    if (L.n_cols > 1) {  // fq_jit_scan(col0 .. col{K-1}, n, head, R, ...); head < 0: the 8-byte path
+        const void *cols[FQ_MAX_SCAN_COLS];
+        void *args[FQ_MAX_SCAN_COLS + 6];
+        int na = 0;
+        for (int j = 0; j < L.n_cols; ++j) {
+            cols[j] = L.cols[j];
+            args[na++] = &cols[j];
+        }
+        if (!L.vec) head = -1;
+        args[na++] = &n;
+        args[na++] = &head;
+        args[na++] = &R;
+        args[na++] = &bitmap;
+        args[na++] = &hc;
+        args[na++] = &parts;
+        FQ_HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)L.grid, 1, 1, kThreads, 1, 1, 0, L.stream, args, nullptr));
+        g_jit_launches += 1;
+        *used = true;
+        return FQ_OK;
+    }
     void *args[] = {&col, &n, &head, &R, &bitmap, &hc, &parts};
     FQ_HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)L.grid, 1, 1, kThreads, 1, 1, 0, L.stream, args, nullptr));
     g_jit_launches += 1;

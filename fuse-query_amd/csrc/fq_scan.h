@@ -28,12 +28,37 @@ struct Launch {
     Partial *parts;
     int grid;
     hipStream_t stream;
+    // fq_aggregate_columns with more than one column (else n_cols == 0): the
+    // columns, their dtypes, and whether they share the 16-byte phase that the
+    // vector loads need (flat mode: one `head`; block mode: all aligned) --
+    // when they do not, the whole scan reads 8 bytes at a time
+    int n_cols;
+    const void *cols[FQ_MAX_SCAN_COLS];
+    int32_t cdt[FQ_MAX_SCAN_COLS];
+    bool vec;
 };
 
 // Host lowering (fq_aggregate.hip): fq_expr -> KProg (res_dtype = result
 // type) and fq_pred -> KPred.
 fq_status lower_expr(const fq_expr &e, int32_t col_dtype, KProg &out, int32_t &res_dtype);
 fq_status lower_pred(const fq_pred *pred, int32_t col_dtype, int64_t len, bool need_data, KPred &out);
+// The same over the n_cols columns of fq_aggregate_columns (dtypes cdt): the
+// column indices in the steps' `bits` / the predicates' `rhs_bits` are read and
+// checked, FQ_OP_LOAD is accepted.
+fq_status lower_expr_cols(const fq_expr &e, const int32_t *cdt, int n_cols, KProg &out, int32_t &res_dtype);
+fq_status lower_pred_cols(const fq_pred *pred, const int32_t *cdt, int n_cols, int64_t len, bool need_data,
+                          KPred &out);
+
+// Flat scan over K >= 2 columns: 16-byte vectors per lane per column in a
+// tile, the next tile's as many in flight.  One column holds 2 x 4; K columns
+// share that budget (2 x K x U <= 8 up to K = 4) so that the registers a lane
+// ties up in loads, and with them the waves per SIMD, stay where the
+// single-column kernel has them.
+// (FQ_SCAN_COLS_VECTORS_3: the A/B of three and four columns, 1 against 2.)
+#ifndef FQ_SCAN_COLS_VECTORS_3
+#define FQ_SCAN_COLS_VECTORS_3 1
+#endif
+inline int scan_cols_vectors(int n_cols) { return n_cols <= 2 ? 2 : FQ_SCAN_COLS_VECTORS_3; }
 
 // Launches the scan of `L` from a specialised kernel when the JIT policy
 // (fq_jit_config) selects it -- or, with `force` (expression trees, which the

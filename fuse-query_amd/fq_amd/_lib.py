@@ -23,7 +23,7 @@ GPU_SYMBOLS = [
     "fq_predicate_bitmap", "fq_group_partition_workspace_bytes", "fq_group_aggregate_partitioned",
     "fq_group_dense_keys", "fq_group_table_merge", "fq_tune_set", "fq_tune_get", "fq_tune_reset",
     "fq_tune_jit_dump_dir", "fq_filter_project_blocks_workspace_bytes", "fq_filter_project_blocks",
-    "fq_blocks_compact_workspace_bytes", "fq_blocks_compact",
+    "fq_blocks_compact_workspace_bytes", "fq_blocks_compact", "fq_aggregate_columns", "fq_jit_prepare_columns",
 ]
 
 
@@ -64,6 +64,10 @@ _protos = {
     "fq_aggregate_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "fq_aggregate": (C.c_int32, [P(abi.fq_col), C.c_int64, P(abi.fq_pred), P(abi.fq_expr),
                                  C.c_uint32, vp, vp, C.c_size_t, vp]),
+    "fq_aggregate_columns": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred), P(abi.fq_expr),
+                                         C.c_uint32, vp, vp, C.c_size_t, vp]),
+    "fq_jit_prepare_columns": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred), P(abi.fq_expr),
+                                           C.c_uint32, P(C.c_int32)]),
     "fq_arith_result_type": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, P(C.c_int32)]),
     "fq_arith": (C.c_int32, [C.c_int32, P(abi.fq_col), P(abi.fq_value), P(abi.fq_col),
                              P(abi.fq_value), P(abi.fq_col), vp, vp]),

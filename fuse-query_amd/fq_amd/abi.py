@@ -33,6 +33,8 @@ DT_BY_NAME = {v: k for k, v in DT_NAMES.items()}
 # operators (src/datavalues/data_value_operator.rs)
 OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MOD = 0, 1, 2, 3, 4
 OP_PUSH = 5  # expression trees: push acc, acc = the column
+OP_LOAD = 6  # fq_aggregate_columns: acc = column `bits` (first step only)
+MAX_SCAN_COLS = 4  # columns of one fq_aggregate_columns scan
 OP_BY_SYM = {"+": OP_ADD, "-": OP_SUB, "*": OP_MUL, "/": OP_DIV, "%": OP_MOD}
 CMP_EQ, CMP_LT, CMP_LTEQ, CMP_GT, CMP_GTEQ = 0, 1, 2, 3, 4
 CMP_BY_SYM = {"=": CMP_EQ, "<": CMP_LT, "<=": CMP_LTEQ, ">": CMP_GT, ">=": CMP_GTEQ}

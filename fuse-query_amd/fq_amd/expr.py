@@ -164,3 +164,110 @@ def pred_tree(col_dtype, leaves, prog):
     pr.tree = C.pointer(t)
     pr._tree = t  # keep the tree alive with the predicate
     return pr
+
+
+# ---- scans over several columns (fq_aggregate_columns) ----
+class Col(int):
+    """Operand marker: column number j of the scan's column list."""
+
+    def __repr__(self):
+        return "Col(%d)" % int(self)
+
+
+def load(j):
+    """First step: the expression starts from column j instead of column 0."""
+    return ("load", int(j))
+
+
+def push(j):
+    """Step: push acc, restart from column j (expression trees)."""
+    return ("push", int(j))
+
+
+def chain_columns(col_dtypes, steps):
+    """chain() over the columns of one block: steps = [load(j)] (first only),
+    push(j), (sym, operand[, reversed]) with operand a constant, Col(j) or
+    STACK.  Column references go into the steps' `bits` (include/fq_gpu.h).
+    Returns (fq_expr, out_dtype)."""
+    e = abi.fq_expr()
+    if len(steps) > abi.MAX_STEPS:
+        raise ValueError("too many steps")
+    acc = col_dtypes[0]
+    stack = []
+    for i, st in enumerate(steps):
+        s = e.steps[i]
+        if st[0] == "load":
+            if i != 0:
+                raise ValueError("load is the first step only")
+            acc = col_dtypes[st[1]]
+            s.op, s.operand, s.reversed, s.dtype, s.bits = abi.OP_LOAD, abi.OPERAND_CONST, 0, acc, st[1]
+            continue
+        if st[0] == "push":
+            j = st[1] if len(st) > 1 else 0
+            stack.append(acc)
+            acc = col_dtypes[j]
+            s.op, s.operand, s.reversed, s.dtype, s.bits = abi.OP_PUSH, abi.OPERAND_CONST, 0, acc, j
+            continue
+        sym, operand = st[0], st[1]
+        rev = bool(st[2]) if len(st) > 2 else False
+        if isinstance(operand, Col):
+            odt, okind, obits = col_dtypes[operand], abi.OPERAND_COLUMN, int(operand)
+        elif operand is STACK or operand == STACK:
+            odt, okind, obits = stack.pop(), abi.OPERAND_STACK, 0
+        elif operand is COL or operand == COL:
+            odt, okind, obits = col_dtypes[0], abi.OPERAND_COLUMN, 0
+        else:
+            val, odt = literal(operand)
+            okind = abi.OPERAND_CONST
+        dt = numerical_coercion(sym, odt, acc) if rev else numerical_coercion(sym, acc, odt)
+        if okind == abi.OPERAND_CONST:
+            obits = to_bits(val, dt)
+        s.op, s.operand, s.reversed, s.dtype, s.bits = abi.OP_BY_SYM[sym], okind, 1 if rev else 0, dt, obits
+        acc = dt
+    e.n_steps = len(steps)
+    e.out_dtype = acc
+    return e, acc
+
+
+def predicate_columns(col_dtypes, lhs_steps, cmp_sym, rhs, flipped=False):
+    """predicate() over the columns of one block: rhs a constant or Col(j)."""
+    p = abi.fq_pred()
+    p.kind = abi.PRED_EXPR
+    lhs, ldt = chain_columns(col_dtypes, lhs_steps)
+    p.lhs = lhs
+    if isinstance(rhs, Col):
+        rdt = col_dtypes[rhs]
+        p.rhs_operand = abi.OPERAND_COLUMN
+        p.rhs_bits = int(rhs)
+    else:
+        val, rdt = literal(rhs)
+        p.rhs_operand = abi.OPERAND_CONST
+    cdt = equal_coercion(cmp_sym, ldt, rdt)
+    cmp = abi.CMP_BY_SYM[cmp_sym]
+    p.cmp = abi.CMP_FLIP[cmp] if flipped else cmp
+    p.cmp_dtype = cdt
+    if p.rhs_operand == abi.OPERAND_CONST:
+        p.rhs_bits = to_bits(val, cdt)
+    return p
+
+
+def pred_tree_columns(col_dtypes, leaves, prog):
+    """pred_tree() whose leaves = [(lhs_steps, cmp_sym, rhs)] may read
+    different columns."""
+    t = abi.fq_pred_tree()
+    if not 1 <= len(leaves) <= abi.MAX_PRED_LEAVES:
+        raise ValueError("1..%d leaves" % abi.MAX_PRED_LEAVES)
+    t.n_leaves = len(leaves)
+    for i, (steps, cmp_sym, rhs) in enumerate(leaves):
+        p = predicate_columns(col_dtypes, steps, cmp_sym, rhs)
+        lf = t.leaves[i]
+        lf.cmp, lf.cmp_dtype, lf.rhs_operand, lf.rhs_bits, lf.lhs = p.cmp, p.cmp_dtype, p.rhs_operand, p.rhs_bits, p.lhs
+    toks = [(abi.PRED_AND if x == "and" else abi.PRED_OR) if isinstance(x, str) else int(x) for x in prog]
+    t.n_prog = len(toks)
+    for i, x in enumerate(toks):
+        t.prog[i] = x
+    pr = abi.fq_pred()
+    pr.kind = abi.PRED_TREE
+    pr.tree = C.pointer(t)
+    pr._tree = t  # keep the tree alive with the predicate
+    return pr

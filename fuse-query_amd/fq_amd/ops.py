@@ -189,6 +189,27 @@ def aggregate(col, block_rows=0, pred=None, value=None, mask=0xF, ws=None, strea
     return state_from_device(t)
 
 
+def aggregate_columns_async(cols, block_rows=0, pred=None, value=None, mask=0xF, ws=None, out=None, stream=None):
+    """Launch fq_aggregate_columns over a list of DeviceColumns of one block
+    (expr.chain_columns / predicate_columns number them by position); returns
+    the device tensor holding the fq_agg_state."""
+    require_gpu()
+    ws = ws or Workspace(lib.fq_aggregate_workspace_bytes(cols[0].len if cols else 0))
+    if out is None:
+        out = torch.empty(48, dtype=torch.uint8, device="cuda")
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    check(lib.fq_aggregate_columns(arr, len(cols), block_rows, C.byref(pred) if pred is not None else None,
+                                   C.byref(value) if value is not None else None, mask,
+                                   C.c_void_p(out.data_ptr()), ws.ptr, ws.nbytes, _stream(stream)))
+    return out
+
+
+def aggregate_columns(cols, block_rows=0, pred=None, value=None, mask=0xF, ws=None, stream=None):
+    """Fused AggregatePartial over up to abi.MAX_SCAN_COLS columns of one
+    device block -> host fq_agg_state."""
+    return state_from_device(aggregate_columns_async(cols, block_rows, pred, value, mask, ws, None, stream))
+
+
 def state_values(st):
     """fq_agg_state -> dict(sum, max, min, count, blocks, flags) of Python values."""
     dt = st.dtype
@@ -386,6 +407,17 @@ def jit_prepare(dtype, pred=None, value=None, mask=abi.AGG_SUM, block_rows=0, le
     out = C.c_int32(0)
     check(lib.fq_jit_prepare(C.byref(c), int(block_rows), C.byref(pred) if pred is not None else None,
                              C.byref(value) if value is not None else None, mask, C.byref(out)))
+    return bool(out.value)
+
+
+def jit_prepare_columns(dtypes, pred=None, value=None, mask=abi.AGG_SUM, block_rows=0, length=1 << 30, lengths=None):
+    """jit_prepare for fq_aggregate_columns: one dtype per column (`lengths`:
+    one length per column, default `length` for all)."""
+    lens = list(lengths) if lengths is not None else [int(length)] * len(dtypes)
+    arr = (abi.fq_col * max(len(dtypes), 1))(*[abi.fq_col(None, int(n), dt, 0) for dt, n in zip(dtypes, lens)])
+    out = C.c_int32(0)
+    check(lib.fq_jit_prepare_columns(arr, len(dtypes), int(block_rows), C.byref(pred) if pred is not None else None,
+                                     C.byref(value) if value is not None else None, mask, C.byref(out)))
     return bool(out.value)
 
 

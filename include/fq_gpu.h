@@ -76,6 +76,7 @@ typedef int32_t fq_status;
 #define FQ_OP_DIV 3
 #define FQ_OP_MOD 4 /* EXTENSION: '%' has no arm in function_factory.rs:17-39 */
 #define FQ_OP_PUSH 5 /* fq_step only: push acc, acc = the column (see FQ_OPERAND_STACK) */
+#define FQ_OP_LOAD 6 /* fq_step only, fq_aggregate_columns: acc = column[bits] (no push) */
 
 #define FQ_CMP_EQ 0
 #define FQ_CMP_LT 1
@@ -243,6 +244,31 @@ fq_status fq_aggregate(const fq_col *col, int64_t block_rows, const fq_pred *pre
                        const fq_expr *value, uint32_t agg_mask, fq_agg_state *d_out,
                        void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- The same scan over up to FQ_MAX_SCAN_COLS 64-bit columns of one block ----
+ * (`sum(a * b) WHERE c < k`: Function trees range over every field of a
+ * DataBlock, function_field.rs:33-40).  cols[0..n_cols) have equal len and a
+ * dtype each among UINT64 / INT64 / FLOAT64 (FQ_E_UNSUPPORTED for a narrow
+ * one).  Column references use fields that the single-column entry points
+ * ignore:
+ *   - a step with operand FQ_OPERAND_COLUMN reads column `bits`;
+ *   - FQ_OP_PUSH restarts acc from column `bits`;
+ *   - an expression starts as column 0 unless its first step is FQ_OP_LOAD,
+ *     which starts it as column `bits`;
+ *   - a predicate (or tree leaf) with rhs_operand FQ_OPERAND_COLUMN compares
+ *     against column `rhs_bits`.
+ * Each step's dtype is the coerced type; the casts of acc and of the operand
+ * column (from that column's own dtype) are inserted by the library with the
+ * rules of fq_aggregate.  Errors keep the reference's order: a predicate
+ * error on any row, then a value error on a kept row only.  Workspace,
+ * block_rows, predicate kinds, flags and the fixed-order fold are
+ * fq_aggregate's; with n_cols == 1 the call IS fq_aggregate.  Scans over more
+ * than one column run on hipRTC-specialised kernels only, whatever min_rows
+ * says (FQ_E_UNSUPPORTED with FQ_JIT_OFF or without hipRTC).                */
+#define FQ_MAX_SCAN_COLS 4
+fq_status fq_aggregate_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                               const fq_pred *pred, const fq_expr *value, uint32_t agg_mask,
+                               fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream);
+
 /* ---- ArithmeticFunction::eval (data_array_arithmetic.rs:14-55) ----
  * Exactly one of {lhs, lhs_scalar} and one of {rhs, rhs_scalar} is non-NULL.
  * out->data must hold out->len elements of the coercion type returned by
@@ -372,6 +398,11 @@ fq_status fq_jit_get_stats(fq_jit_stats *out);
  * compiled for gfx950 only to validate it.                                  */
 fq_status fq_jit_prepare(const fq_col *col, int64_t block_rows, const fq_pred *pred,
                          const fq_expr *value, uint32_t agg_mask, int32_t *specialised);
+/* The same for fq_aggregate_columns (the columns' data may be NULL: they then
+ * count as 16-byte aligned). */
+fq_status fq_jit_prepare_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                                 const fq_pred *pred, const fq_expr *value, uint32_t agg_mask,
+                                 int32_t *specialised);
 
 /* ---- Launch-shape knobs (tuning tools only; no reference counterpart) ----
  * Every knob has a compiled-in default, the measured best on MI355X

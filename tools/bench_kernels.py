@@ -8,6 +8,7 @@ of R repetitions; achieved GB/s = algorithmic bytes / time.  Results are
 checked against numpy on a prefix.  Prints one JSON document.
 
 usage: python tools/bench_kernels.py [--rows 1.25e9] [--reps 10] > gpurun_out/kernels.json
+       python tools/bench_kernels.py --only q6 [--q6-rows 134217728] [--reps 20]   (the q6 lines alone)
 """
 import argparse
 import ctypes as C
@@ -47,14 +48,133 @@ def timed(fn, reps):
     return statistics.median(ts)
 
 
+def timed_all(fn, reps, warm=3):
+    """every sample (ms) of `reps` event-timed calls after `warm` untimed ones"""
+    s = torch.cuda.current_stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0.record(s)
+        fn()
+        e1.record(s)
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return ts
+
+
+def q6_lines(n, reps, st, res):
+    """q6 sum(a*b) where c<k, 3 u64 columns: ONE fq_aggregate_columns scan (24 B/row), beside the
+    single-column scans timed in the same process and the unfused path for the same statement (what
+    engine/functions.cpp AggregatorFunction::summarize runs when the shape does not fuse: fq_compare,
+    a bitmap probe scan, fq_filter_compact of every column, fq_arith on the kept rows, an identity
+    scan), every launch event-timed."""
+    from fq_amd.expr import Col, chain_columns, load, predicate_columns
+    U = abi.DT_UINT64
+    k38 = (3 * 2**64) // 8  # keeps ~3/8 of the rows
+    c, a, b = (ops.splitmix_column(seed, 0, n) for seed in (101, 102, 103))
+    dts = [U, U, U]
+    pred = predicate_columns(dts, [], "<", k38)
+    value, _ = chain_columns(dts, [load(1), ("*", Col(2))])
+    cols = (abi.fq_col * 3)(c.col(), a.col(), b.col())
+    aws = ops.Workspace(lib.fq_aggregate_workspace_bytes(n))
+    dst = torch.empty(48, dtype=torch.uint8, device="cuda")
+    SC = abi.AGG_SUM | abi.AGG_COUNT
+
+    def rec(name, ts, nbytes, note=""):
+        ms = statistics.median(ts)
+        gbps = nbytes / (ms * 1e-3) / 1e9
+        res.append({"kernel": name, "ms": ms, "ms_min": min(ts), "ms_max": max(ts), "reps": len(ts),
+                    "algorithmic_bytes": nbytes, "achieved_gbps": gbps, "frac_of_peak": gbps / PEAK, "note": note})
+        print("%-58s %8.3f ms [%.3f .. %.3f]  %7.0f GB/s  %4.1f %%" % (name, ms, min(ts), max(ts), gbps,
+                                                                     100 * gbps / PEAK), file=sys.stderr)
+        return ms
+
+    def fused(br, mask):
+        check(lib.fq_aggregate_columns(cols, 3, br, C.byref(pred), C.byref(value), mask,
+                                       C.c_void_p(dst.data_ptr()), aws.ptr, aws.nbytes, st))
+
+    def single(col, p, v, mask, br):
+        cc = col.col()
+        check(lib.fq_aggregate(C.byref(cc), br, C.byref(p), C.byref(v), mask, C.c_void_p(dst.data_ptr()), aws.ptr,
+                               aws.nbytes, st))
+
+    f_flat = rec("q6 sum(a*b) where c<k, 3 u64 columns", timed_all(lambda: fused(0, SC), reps), 24 * n,
+                 "one DataBlock (block_rows 0): flat scan")
+    got = ops.state_from_device(dst)
+    hc, ha, hb = (x.to_numpy() for x in (c, a, b))
+    keep = hc < np.uint64(k38)
+    with np.errstate(over="ignore"):
+        want = int((ha[keep] * hb[keep]).sum(dtype=np.uint64))
+    assert got.count == int(keep.sum()) and got.sum == want and got.flags == 0, (got.count, got.sum, want)
+    rec("q6 max(a*b) where c<k, 3 u64 columns", timed_all(lambda: fused(10000, abi.AGG_MAX | abi.AGG_COUNT), reps),
+        24 * n, "flat scan, as the single-column C4 line")
+    f_blk = rec("q6 sum(a*b) where c<k, 3 u64 columns, 10,000-row blocks",
+                timed_all(lambda: fused(10000, SC), reps), 24 * n, "block mode: one wave per reference block")
+    got = ops.state_from_device(dst)
+    assert got.count == int(keep.sum()) and got.sum == want and got.flags == 0
+    v1, _ = chain(U, [("+", 1)])
+    p1 = predicate(U, [("%", 8)], "<", 3)
+    rec("single column: max(x+1) where x%8<3", timed_all(lambda: single(a, p1, v1, abi.AGG_MAX | abi.AGG_COUNT, 10000),
+                                                         reps), 8 * n, "C4 shape, flat scan, same process")
+    rec("single column: sum(x+1) where x%8<3, 10,000-row blocks",
+        timed_all(lambda: single(a, p1, v1, SC, 10000), reps), 8 * n, "block mode, same process")
+
+    # the unfused path for the same statement (this tree, what runs with the JIT off)
+    bm = ops.empty_column(n, abi.DT_BOOLEAN)
+    kc, ka, kb, prod = (ops.empty_column(n, U) for _ in range(4))
+    fws = ops.Workspace(lib.fq_filter_workspace_bytes(n))
+    bound = abi.fq_value(U, 1, k38)
+    kept = C.c_int64(0)
+    pb = abi.fq_pred()
+    pb.kind = abi.PRED_BITMAP
+    pb.bitmap = bm.ptr
+    cc = c.col()
+
+    def unfused():
+        check(lib.fq_compare(abi.CMP_BY_SYM["<"], C.byref(cc), None, None, C.byref(bound), C.c_void_p(bm.ptr), n,
+                             None, st))
+        check(lib.fq_aggregate(C.byref(cc), 0, C.byref(pb), None, SC, C.c_void_p(dst.data_ptr()), aws.ptr,
+                               aws.nbytes, st))
+        for src, out in ((c, kc), (a, ka), (b, kb)):
+            sc = src.col()
+            check(lib.fq_filter_compact(C.byref(sc), C.c_void_p(bm.ptr), C.c_void_p(out.ptr), C.byref(kept), fws.ptr,
+                                        fws.nbytes, st))
+        m = kept.value
+        lc = abi.fq_col(C.c_void_p(ka.ptr), m, U, 0)
+        rc = abi.fq_col(C.c_void_p(kb.ptr), m, U, 0)
+        oc = abi.fq_col(C.c_void_p(prod.ptr), m, U, 0)
+        check(lib.fq_arith(abi.OP_BY_SYM["*"], C.byref(lc), None, C.byref(rc), None, C.byref(oc), None, st))
+        check(lib.fq_aggregate(C.byref(oc), 0, None, None, SC, C.c_void_p(dst.data_ptr()), aws.ptr, aws.nbytes, st))
+
+    ts = timed_all(unfused, reps)
+    m = kept.value
+    got = ops.state_from_device(dst)
+    assert got.count == int(keep.sum()) == m and got.sum == want
+    moved = (8 * n + n // 8) * 2 + 3 * (8 * n + n // 8 + 8 * m) + 24 * m + 8 * m
+    u = rec("q6 unfused: compare, probe, 3 compactions, arith, scan", ts, moved,
+            "this tree with the JIT off; includes fq_filter_compact's host syncs; bytes = what the path moves")
+    res.append({"q6_fused_over_unfused": {"flat": u / f_flat, "block_mode": u / f_blk,
+                                          "bytes_ratio": moved / (24 * n)}})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=float, default=1.25e9)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--only", choices=["q6"], default=None, help="run only the named group of lines")
+    ap.add_argument("--q6-rows", type=float, default=float(1 << 27))
     args = ap.parse_args()
     n = int(args.rows)
     st = ops._stream()
     res = []
+    if args.only == "q6":
+        q6_lines(int(args.q6_rows), args.reps, st, res)
+        print(json.dumps({"rows": int(args.q6_rows), "peak_gbps": PEAK, "device": torch.cuda.get_device_name(0),
+                          "kernels": res}, indent=1))
+        return
 
     def rec(name, ref, ms, nbytes, note=""):
         gbps = nbytes / (ms * 1e-3) / 1e9
@@ -226,6 +346,8 @@ def main():
     ms = timed(group_high, max(3, args.reps // 3))
     rec("group by x (distinct, %d rows): count" % hn, "high cardinality: HBM table, 2^28 slots", ms, 8 * hn,
         "includes the table init (4 GB)")
+
+    q6_lines(int(args.q6_rows), args.reps, st, res)
 
     print(json.dumps({"rows": n, "peak_gbps": PEAK, "device": torch.cuda.get_device_name(0),
                       "kernels": res}, indent=1))

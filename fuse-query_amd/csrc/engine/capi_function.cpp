@@ -264,6 +264,131 @@ fq_status fq_functions_accumulate(fq_engine *e, fq_function *const *fs, int32_t 
     });
 }
 
+}  // extern "C"
+
+namespace {
+
+// one evaluated column's bytes (Boolean: its bitmap words)
+size_t column_bytes(const fq::Column &c) {
+    return c.dtype == FQ_DT_BOOLEAN ? (size_t)((c.len + 63) / 64) * 8 : (size_t)c.len * (size_t)fq::dtype_size(c.dtype);
+}
+
+// `for func in funcs { func.eval(&block)?.to_array(block.num_rows()) }` over a
+// plain block (transform_projection.rs:45-56)
+std::vector<fq::Column> eval_each(fq_function *const *fs, int32_t n, const fq::DataBlock &blk, fq::ExecCtx &ctx) {
+    std::vector<fq::Column> cols;
+    const int64_t rows = blk.num_rows();
+    for (int32_t i = 0; i < n; ++i) {
+        fq::Column c = fs[i]->f->eval(blk, ctx).to_array(rows, ctx);
+        if (c.len > 0 && !c.on_device()) throw fq::FQException(FQ_E_UNSUPPORTED, "fq_functions_eval: host column result");
+        cols.push_back(c);
+    }
+    return cols;
+}
+
+}  // namespace
+
+extern "C" {
+
+fq_status fq_functions_eval(fq_engine *e, fq_function *const *fs, int32_t n, const fq_block *b, void *const *d_out,
+                            size_t cap, int64_t *d_counts, int32_t *out_dtypes, int64_t *out_len, size_t *out_bytes,
+                            int32_t *fused) {
+    if (!e || !b || n < 1 || !fs || !d_out || !out_dtypes || !out_len || !out_bytes || !fused)
+        return fqc::fail(FQ_E_INVALID, "fq_functions_eval: bad argument");
+    for (int32_t i = 0; i < n; ++i)
+        if (!fs[i]) return fqc::fail(FQ_E_INVALID, "fq_functions_eval: NULL function");
+    *out_len = 0;
+    *out_bytes = 0;
+    *fused = 0;
+    return guard([&] {
+        fq::ExecCtx ctx(device_runtime(e));
+        const fq::DataBlock blk = borrow_block(*b);
+        const int64_t rows = blk.columns.empty() ? 0 : blk.columns[0].len;
+        const int64_t B = blk.sub_block_rows;
+        const bool blocks = d_counts != nullptr;
+        const size_t full = (size_t)rows * 8;  // a 64-bit output of every row
+        if (blocks && B < FQ_PROJECT_MIN_BLOCK_ROWS)
+            throw fq::FQException(FQ_E_INVALID, "fq_functions_eval: block geometry needs block_rows >= "
+                                                "FQ_PROJECT_MIN_BLOCK_ROWS");
+        if (blocks && cap < full) {
+            *out_bytes = full;
+            throw fq::FQException(FQ_E_INVALID, "fq_functions_eval: output buffers too small");
+        }
+        for (int32_t i = 0; i < n; ++i)
+            if (rows > 0 && cap > 0 && !d_out[i]) throw fq::FQException(FQ_E_INVALID, "fq_functions_eval: NULL output");
+        auto copy_out = [&](const fq::Column &c, void *dst, size_t bytes) {
+            if (bytes > 0)
+                fq::check_hip(hipMemcpyAsync(dst, c.dptr(), bytes, hipMemcpyDeviceToDevice, ctx.stream()), "hipMemcpyAsync");
+        };
+
+        // one fused kernel: straight into the caller's buffers when they hold
+        // every row (the kept rows are not known before it runs)
+        if (n <= FQ_MAX_PROJECT && rows > 0) {
+            std::vector<fq::FunctionRef> funcs;
+            for (int32_t i = 0; i < n; ++i) funcs.push_back(fs[i]->f);
+            const bool direct = cap >= full;
+            const fq::ProjectInto into{d_out, d_counts};
+            fq::DataBlock out;
+            bool one_kernel = false;
+            if (fq::project_fused(blk, funcs, blk.schema, ctx, out, blocks, nullptr, direct ? &into : nullptr, &one_kernel)) {
+                const int64_t kept = out.layout ? out.layout->rows : out.num_rows();
+                for (int32_t i = 0; i < n; ++i) out_dtypes[i] = out.columns[(size_t)i].dtype;
+                *out_len = kept;
+                *out_bytes = blocks ? full : (size_t)kept * 8;
+                *fused = one_kernel ? 1 : 0;  // 0: the filter's bitmap came from its own kernels first
+                if (!direct) {
+                    if (*out_bytes > cap) throw fq::FQException(FQ_E_INVALID, "fq_functions_eval: output buffers too small");
+                    for (int32_t i = 0; i < n; ++i) copy_out(out.columns[(size_t)i], d_out[i], *out_bytes);
+                }
+                ctx.sync();
+                return;
+            }
+        }
+
+        if (!blocks) {  // materialise once, evaluate each function, to_array, copy out
+            const fq::DataBlock plain = fq::needs_materialize(blk) ? fq::materialize(blk, ctx) : blk;
+            const std::vector<fq::Column> cols = eval_each(fs, n, plain, ctx);
+            for (int32_t i = 0; i < n; ++i) {
+                out_dtypes[i] = cols[(size_t)i].dtype;
+                *out_bytes = std::max(*out_bytes, column_bytes(cols[(size_t)i]));
+            }
+            *out_len = plain.num_rows();
+            if (*out_bytes > cap) throw fq::FQException(FQ_E_INVALID, "fq_functions_eval: output buffers too small");
+            for (int32_t i = 0; i < n; ++i) copy_out(cols[(size_t)i], d_out[i], column_bytes(cols[(size_t)i]));
+            ctx.sync();
+            return;
+        }
+
+        // block geometry, not fusable: the reference's loop itself -- filter and
+        // project each reference block on its own, its rows left where the block starts
+        const int64_t nb = rows == 0 ? 0 : (rows + B - 1) / B;
+        std::vector<int64_t> counts((size_t)nb, 0);
+        int64_t kept = 0;
+        for (int64_t k = 0; k < nb; ++k) {
+            fq::DataBlock one = blk;
+            one.sub_block_rows = 0;
+            for (auto &c : one.columns) c = c.slice(k * B, std::min(B, rows - k * B));
+            const fq::DataBlock plain = fq::needs_materialize(one) ? fq::materialize(one, ctx) : one;
+            const std::vector<fq::Column> cols = eval_each(fs, n, plain, ctx);
+            for (int32_t i = 0; i < n; ++i) {
+                const fq::Column &c = cols[(size_t)i];
+                if (fq::dtype_size(c.dtype) != 8 || c.dtype == FQ_DT_BOOLEAN)
+                    throw fq::FQException(FQ_E_UNSUPPORTED, "fq_functions_eval: block geometry holds 64-bit outputs only");
+                out_dtypes[i] = c.dtype;
+                copy_out(c, (char *)d_out[i] + (size_t)(k * B) * 8, column_bytes(c));
+            }
+            counts[(size_t)k] = plain.num_rows();
+            kept += plain.num_rows();
+        }
+        if (nb > 0)
+            fq::check_hip(hipMemcpyAsync(d_counts, counts.data(), (size_t)nb * 8, hipMemcpyHostToDevice, ctx.stream()),
+                          "hipMemcpyAsync");
+        *out_len = kept;
+        *out_bytes = full;
+        ctx.sync();
+    });
+}
+
 fq_status fq_function_accumulate_result(const fq_function *f, fq_scalar *states, size_t cap, size_t *n) {
     if (!f || !n || (cap > 0 && !states)) return fqc::fail(FQ_E_INVALID, "fq_function_accumulate_result: bad argument");
     return guard([&] {

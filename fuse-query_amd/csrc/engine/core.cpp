@@ -890,6 +890,20 @@ Column Column::device(DataType dt, int64_t len, hipStream_t st) {
     return c;
 }
 
+Column Column::borrowed(DataType dt, int64_t len, void *d_ptr) {
+    Column c;
+    c.dtype = dt;
+    c.len = len;
+    auto *db = new DeviceBuffer();
+    db->ptr = d_ptr;
+    db->async = false;
+    c.dev = std::shared_ptr<DeviceBuffer>(db, [](DeviceBuffer *p) {
+        p->ptr = nullptr;  // borrowed
+        delete p;
+    });
+    return c;
+}
+
 Column Column::host_values(DataType dt, std::vector<DataValue> rows) {
     Column c;
     c.dtype = dt;

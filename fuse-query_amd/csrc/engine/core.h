@@ -351,6 +351,7 @@ struct Column {
     void *dptr() const { return dev ? (char *)dev->ptr + offset : nullptr; }
     fq_col abi() const;
     static Column device(DataType dt, int64_t len, hipStream_t st);  // uninitialised
+    static Column borrowed(DataType dt, int64_t len, void *d_ptr);   // the caller's device buffer: never freed here
     static Column host_values(DataType dt, std::vector<DataValue> rows);
     static Column host_flat(DataType dt, std::vector<uint64_t> bits);
     Column slice(int64_t start, int64_t n) const;

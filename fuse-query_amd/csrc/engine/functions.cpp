@@ -670,19 +670,37 @@ FunctionRef function_factory(const std::string &name, std::vector<FunctionRef> a
 // ---------------------------------------------------------------------------
 // predicate evaluation + compaction (FilterTransform::expression_executor)
 // ---------------------------------------------------------------------------
-// A predicate over one 64-bit device column as ONE hipRTC kernel
-// (fq_predicate_bitmap) instead of a kernel per Function node; false when the
-// shape is not fusable or the JIT is off/unavailable (the caller evaluates
-// the Function tree).
+// The device columns a fused row kernel reads, in `cols`' order; false when one
+// is not 64-bit device data (or, with several, not UInt64 / Int64 / Float64).
+static bool fused_device_columns(const DataBlock &b, const FusedColumns &cols, std::vector<Column> &out,
+                                 fq_col (&abi)[FQ_MAX_SCAN_COLS]) {
+    out.clear();
+    for (size_t j = 0; j < cols.names.size(); ++j) {
+        const Column &c = b.column_by_name(cols.names[j]);
+        if (!c.on_device() || dtype_size(c.dtype) != 8 || c.dtype == FQ_DT_BOOLEAN) return false;
+        if (cols.names.size() > 1 && !is_chain_dtype(c.dtype)) return false;
+        out.push_back(c);
+        abi[j] = c.abi();
+    }
+    return !out.empty();
+}
+
+// A predicate over up to FQ_MAX_SCAN_COLS 64-bit device columns as ONE hipRTC
+// kernel (fq_predicate_bitmap_columns) instead of a kernel per Function node;
+// false when the shape is not fusable or the JIT is off/unavailable (the
+// caller evaluates the Function tree).
 static bool fused_predicate_bitmap(Function &pred, const DataBlock &b, ExecCtx &ctx, Column &out) {
     FusedPred fp;
-    if (!b.schema || !pred.to_pred(*b.schema, fp)) return false;
-    const Column &c = b.column_by_name(fp.column);
-    if (!c.on_device() || dtype_size(c.dtype) != 8) return false;
+    FusedColumns cols;
+    if (!b.schema || !pred.to_pred(*b.schema, fp, &cols)) return false;
+    std::vector<Column> cs;
+    fq_col ics[FQ_MAX_SCAN_COLS];
+    if (!fused_device_columns(b, cols, cs, ics)) return false;
+    const Column &c = cs[0];
     Column bm = Column::device(FQ_DT_BOOLEAN, c.len, ctx.stream());
     auto flag = DeviceBuffer::alloc(sizeof(uint32_t), ctx.stream());
-    fq_col ic = c.abi();
-    const fq_status st = fq_predicate_bitmap(&ic, fp.get(), (uint64_t *)bm.dptr(), (uint32_t *)flag->ptr, ctx.stream());
+    const fq_status st = fq_predicate_bitmap_columns(ics, (int32_t)cs.size(), fp.get(), (uint64_t *)bm.dptr(),
+                                                     (uint32_t *)flag->ptr, ctx.stream());
     if (st == FQ_E_UNSUPPORTED) return false;  // no hipRTC / JIT off / shape outside it: per node (same errors)
     check_fq(st);
     out = bm;
@@ -795,18 +813,22 @@ DataBlock materialize(const DataBlock &b, ExecCtx &ctx) {
 // memset + copy 24.36 / 23.52 ms per query, this 23.94 / 23.33, the hand-off
 // alone with the pipe polling the words 24.03 / 23.52 -- the first pair with an
 // event pair around every launch, the second with one span per query.
-static bool project_blocks(const DataBlock &b, const Column &c, const fq_pred *pred, std::vector<fq_expr> &exprs,
+static bool project_blocks(const DataBlock &b, const std::vector<Column> &cs, const fq_pred *pred, std::vector<fq_expr> &exprs,
                            std::vector<Column> &outs, std::vector<void *> &ptrs, const SchemaRef &schema, ExecCtx &ctx,
-                           DataBlock &out, LaunchSpan *span) {
+                           DataBlock &out, LaunchSpan *span, const ProjectInto *into) {
+    const Column &c = cs[0];
+    const int32_t n_cols = (int32_t)cs.size();
     const int64_t n = c.len, B = b.sub_block_rows;
     const int64_t nb = n <= B ? 1 : (n + B - 1) / B;
     auto layout = std::make_shared<BlockLayout>();
     layout->block_rows = B;
     layout->n_blocks = n == 0 ? 0 : nb;
-    layout->counts = DeviceBuffer::alloc((size_t)std::max<int64_t>(nb, 1) * 8, ctx.stream());
+    if (!into) layout->counts = DeviceBuffer::alloc((size_t)std::max<int64_t>(nb, 1) * 8, ctx.stream());
+    int64_t *const d_counts = into ? into->d_counts : (int64_t *)layout->counts->ptr;
     // the map kernel (no predicate) has its words written by the host and no
     // hand-off: a workspace of its own, zeroed before it, the flags copied after
-    const bool resident = pred && pred->kind != FQ_PRED_NONE;
+    // (and so has a call into the caller's buffers)
+    const bool resident = !into && pred && pred->kind != FQ_PRED_NONE;
     ctx.res->project_resident(ctx.stream());
     uint64_t *res = ctx.res->project_res;
     std::shared_ptr<DeviceBuffer> ws;
@@ -820,13 +842,16 @@ static bool project_blocks(const DataBlock &b, const Column &c, const fq_pred *p
         e0 = ctx.res->take_event();
         e1 = ctx.res->take_event();
     }
-    fq_col ic = c.abi();
+    fq_col ic[FQ_MAX_SCAN_COLS], none[FQ_MAX_SCAN_COLS];
     // the shape's kernel compiled (first use: hipRTC, ~0.2 s) before the
     // queue's launch lock is taken: a zero-length call only prepares it
-    fq_col none = ic;
-    none.len = 0;
-    fq_status st = fqk::filter_project_blocks_enqueue(&none, B, pred, exprs.data(), (int32_t)exprs.size(), ptrs.data(),
-                                                      nullptr, res, nullptr, nullptr, 0, nullptr, nullptr, ctx.stream());
+    for (int32_t j = 0; j < n_cols; ++j) {
+        none[j] = ic[j] = cs[(size_t)j].abi();
+        none[j].len = 0;
+    }
+    fq_status st = fqk::filter_project_blocks_enqueue_columns(none, n_cols, B, pred, exprs.data(), (int32_t)exprs.size(),
+                                                              ptrs.data(), nullptr, res, nullptr, nullptr, 0, nullptr,
+                                                              nullptr, ctx.stream());
     if (st == FQ_E_UNSUPPORTED) return false;
     check_fq(st);
     hipEvent_t done = ctx.res->take_sync_event();
@@ -836,11 +861,11 @@ static bool project_blocks(const DataBlock &b, const Column &c, const fq_pred *p
         // this worker's last hand-off has landed (the pipe waited for it); an
         // empty block launches nothing, so its words must read 0 kept rows
         res[0] = res[1] = 0;
-        st = fqk::filter_project_blocks_enqueue(&ic, B, pred, exprs.data(), (int32_t)exprs.size(), ptrs.data(),
-                                                (int64_t *)layout->counts->ptr, res,
-                                                resident ? ctx.res->project_dres : nullptr,
-                                                resident ? ctx.res->project_ws : ws->ptr,
-                                                fq_filter_project_blocks_workspace_bytes(), e0, e1, ctx.stream());
+        st = fqk::filter_project_blocks_enqueue_columns(ic, n_cols, B, pred, exprs.data(), (int32_t)exprs.size(),
+                                                        ptrs.data(), d_counts, res,
+                                                        resident ? ctx.res->project_dres : nullptr,
+                                                        resident ? ctx.res->project_ws : ws->ptr,
+                                                        fq_filter_project_blocks_workspace_bytes(), e0, e1, ctx.stream());
         if (st == FQ_OK) check_hip(hipEventRecord(done, ctx.stream()), "hipEventRecord");  // after the result words
     }
     if (st == FQ_OK) {
@@ -863,7 +888,8 @@ static bool project_blocks(const DataBlock &b, const Column &c, const fq_pred *p
     S.project_launches++;
     S.project_rows += (uint64_t)n;
     S.project_kept += (uint64_t)kept;
-    S.project_bytes += (uint64_t)n * (uint64_t)dtype_size(c.dtype) + (uint64_t)kept * 8 * (uint64_t)outs.size();
+    // every column read once: 8 bytes per row per column
+    S.project_bytes += (uint64_t)n * (uint64_t)dtype_size(c.dtype) * (uint64_t)n_cols + (uint64_t)kept * 8 * (uint64_t)outs.size();
     out = DataBlock{};
     out.schema = schema;
     out.sub_block_rows = B;
@@ -874,58 +900,80 @@ static bool project_blocks(const DataBlock &b, const Column &c, const fq_pred *p
 }
 
 // ProjectionTransform over a block with a pending filter (or none): when every
-// projected expression is a chain over the same 64-bit device column, one
-// fq_filter_project call compacts and evaluates them together (the predicate
-// fused too when it is over that column, else its bitmap is evaluated
-// first).  false: not fusable, the caller materialises + evaluates.
+// projected expression is a chain or tree over up to FQ_MAX_SCAN_COLS 64-bit
+// device columns, one fq_filter_project_columns call compacts and evaluates
+// them together.  The columns are numbered like AggFusion's: the filter's
+// first, then the expressions' by first appearance.  A filter that does not
+// fuse (or would be the fifth column) has its bitmap evaluated first.  false:
+// not fusable (a fifth column, a ninth step, a narrow or host column, the JIT
+// off), the caller materialises + evaluates.
 bool project_fused(const DataBlock &b, const std::vector<FunctionRef> &funcs, const SchemaRef &schema, ExecCtx &ctx,
-                   DataBlock &out, bool block_stream, LaunchSpan *span) {
+                   DataBlock &out, bool block_stream, LaunchSpan *span, const ProjectInto *into, bool *one_kernel) {
     if (funcs.empty() || funcs.size() > FQ_MAX_PROJECT || !b.schema || b.columns.empty()) return false;
+    // the expressions over the filter's columns; false: a chain does not fuse
+    auto collect = [&](FusedColumns &cols, std::vector<FusedChain> &chains) {
+        for (size_t j = 0; j < funcs.size(); ++j) {
+            if (!funcs[j]->to_chain(*b.schema, chains[j], &cols)) return false;
+            if (dtype_size(chains[j].out_dtype) != 8) return false;
+        }
+        return true;
+    };
     std::vector<FusedChain> chains(funcs.size());
-    bool computes = false;
-    for (size_t j = 0; j < funcs.size(); ++j) {
-        if (!funcs[j]->to_chain(*b.schema, chains[j])) return false;
-        if (chains[j].column != chains[0].column || dtype_size(chains[j].out_dtype) != 8) return false;
-        computes |= chains[j].expr.n_steps > 0;
+    FusedColumns cols;
+    FusedPred fp;
+    bool pred_fused = b.filter && b.filter->to_pred(*b.schema, fp, &cols);
+    if (!pred_fused) cols = FusedColumns{};
+    if (!collect(cols, chains)) {
+        if (!pred_fused) return false;
+        pred_fused = false;  // without the filter's columns the expressions may still fit
+        cols = FusedColumns{};
+        if (!collect(cols, chains)) return false;
     }
-    if (!b.filter && !computes) return false;  // plain column references: zero-copy in the unfused path
-    const Column &c = b.column_by_name(chains[0].column);
-    if (!c.on_device() || dtype_size(c.dtype) != 8 || c.dtype == FQ_DT_BOOLEAN) return false;
+    bool computes = false;
+    for (auto &fc : chains) computes |= fc.expr.n_steps > 0;
+    if (!b.filter && !computes && !into) return false;  // plain column references: zero-copy in the unfused path
+    std::vector<Column> cs;
+    fq_col ics[FQ_MAX_SCAN_COLS];
+    if (!fused_device_columns(b, cols, cs, ics)) return false;
+    const int32_t n_cols = (int32_t)cs.size();
     fq_jit_stats js{};
     if (fq_jit_get_stats(&js) != FQ_OK || js.mode == FQ_JIT_OFF || js.available == 0) return false;
-    FusedPred fp;
+    std::vector<fq_expr> exprs;
+    for (auto &fc : chains) {
+        fq_expr e = fc.expr;
+        if (n_cols > 1 && !fc.with_load(e)) return false;  // no step left for FQ_OP_LOAD
+        exprs.push_back(e);
+    }
     fq_pred bp{};
     const fq_pred *pred = nullptr;
     Column bm;
-    if (b.filter) {
-        if (b.filter->to_pred(*b.schema, fp) && fp.column == chains[0].column) {
-            pred = fp.get();
-        } else {
-            DataBlock nb = b;
-            nb.filter = nullptr;
-            bm = eval_predicate(*b.filter, nb, ctx);
-            bp.kind = FQ_PRED_BITMAP;
-            bp.bitmap = (const uint64_t *)bm.dptr();
-            pred = &bp;
-        }
+    if (one_kernel) *one_kernel = pred_fused || !b.filter;
+    if (pred_fused) {
+        pred = fp.get();
+    } else if (b.filter) {
+        DataBlock nb = b;
+        nb.filter = nullptr;
+        bm = eval_predicate(*b.filter, nb, ctx);
+        bp.kind = FQ_PRED_BITMAP;
+        bp.bitmap = (const uint64_t *)bm.dptr();
+        pred = &bp;
     }
+    const Column &c = cs[0];
     const int64_t n = c.len;
     std::vector<Column> outs;
     std::vector<void *> ptrs;
-    std::vector<fq_expr> exprs;
-    for (auto &fc : chains) {
-        outs.push_back(Column::device(fc.out_dtype, n, ctx.stream()));
+    for (size_t j = 0; j < chains.size(); ++j) {
+        outs.push_back(into ? Column::borrowed(chains[j].out_dtype, n, into->d_out[j])
+                            : Column::device(chains[j].out_dtype, n, ctx.stream()));
         ptrs.push_back(outs.back().dptr());
-        exprs.push_back(fc.expr);
     }
-    if (block_stream && pred && b.sub_block_rows >= FQ_PROJECT_MIN_BLOCK_ROWS)
-        return project_blocks(b, c, pred, exprs, outs, ptrs, schema, ctx, out, span);
-    const size_t wsb = fq_filter_project_workspace_bytes(n);
+    if (into ? into->d_counts != nullptr : (block_stream && pred && b.sub_block_rows >= FQ_PROJECT_MIN_BLOCK_ROWS))
+        return project_blocks(b, cs, pred, exprs, outs, ptrs, schema, ctx, out, span, into);
+    const size_t wsb = fq_filter_project_columns_workspace_bytes(n, n_cols);
     auto ws = DeviceBuffer::alloc(wsb, ctx.stream());
-    fq_col ic = c.abi();
     int64_t kept = 0;
-    const fq_status st = fq_filter_project(&ic, pred, exprs.data(), (int32_t)exprs.size(), ptrs.data(), &kept, ws->ptr,
-                                           wsb, ctx.stream());
+    const fq_status st = fq_filter_project_columns(ics, n_cols, pred, exprs.data(), (int32_t)exprs.size(), ptrs.data(),
+                                                   &kept, ws->ptr, wsb, ctx.stream());
     if (st == FQ_E_UNSUPPORTED) return false;  // the unfused path evaluates it (and raises what the reference does)
     check_fq(st);
     out = DataBlock{};

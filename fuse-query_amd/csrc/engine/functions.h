@@ -493,11 +493,25 @@ class AggFusion {
 // when the predicate is a chain over one 64-bit column, else per node)
 Column eval_predicate(Function &pred, const DataBlock &b, ExecCtx &ctx);
 
+// A fused projection into buffers the caller owns (fq_functions_eval): one per
+// function, each holding the block's rows x 8 bytes.  d_counts set: the
+// block-stream kernel whatever the filter (block b's count to d_counts[b]);
+// null: the contiguous kernel.  Either way the call uses a workspace of its
+// own, zeroed for it, not the worker's resident one.
+struct ProjectInto {
+    void *const *d_out = nullptr;
+    int64_t *d_counts = nullptr;
+};
+
 // ProjectionTransform's expressions (and the block's pending filter) through
-// one fq_filter_project call; false when the shape is not fusable
+// one fq_filter_project_columns / _blocks_columns call; false when the shape is
+// not fusable.  *one_kernel (optional): the filter ran inside that kernel too
+// (false: it did not fuse and its bitmap was evaluated first, node by node)
 bool project_fused(const DataBlock &b, const std::vector<FunctionRef> &funcs, const SchemaRef &schema, ExecCtx &ctx,
                    DataBlock &out,
                    bool block_stream = true,
-                   LaunchSpan *span = nullptr);
+                   LaunchSpan *span = nullptr,
+                   const ProjectInto *into = nullptr,
+                   bool *one_kernel = nullptr);
 
 }  // namespace fq

@@ -900,26 +900,27 @@ static fq_status plan_scan_cols(const fq_col *cols, int32_t n_cols, int64_t bloc
     return FQ_OK;
 }
 
-// argument checks of the two *_columns entry points
-static fq_status check_cols(const fq_col *cols, int32_t n_cols, bool need_data) {
-    if (!cols) return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: NULL argument");
+// argument checks of the *_columns entry points (`who` names the caller in the messages)
+fq_status check_cols(const fq_col *cols, int32_t n_cols, bool need_data, const char *who) {
+    const std::string W = std::string(who) + ": ";
+    if (!cols) return fqc::fail(FQ_E_INVALID, W + "NULL argument");
     if (n_cols < 1 || n_cols > FQ_MAX_SCAN_COLS)
-        return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: n_cols must be 1.." + std::to_string(FQ_MAX_SCAN_COLS) +
+        return fqc::fail(FQ_E_INVALID, W + "n_cols must be 1.." + std::to_string(FQ_MAX_SCAN_COLS) +
                                            ", got " + std::to_string(n_cols));
     for (int j = 0; j < n_cols; ++j) {
-        if (cols[j].len < 0) return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: negative length");
+        if (cols[j].len < 0) return fqc::fail(FQ_E_INVALID, W + "negative length");
         if (cols[j].len != cols[0].len)
-            return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: column " + std::to_string(j) + " has " +
+            return fqc::fail(FQ_E_INVALID, W + "column " + std::to_string(j) + " has " +
                                                std::to_string(cols[j].len) + " rows, column 0 has " +
                                                std::to_string(cols[0].len));
         if (!is_chain_dtype(cols[j].dtype))
-            return fqc::fail(FQ_E_UNSUPPORTED, std::string("fq_aggregate_columns: ") + fqc::dtype_name(cols[j].dtype) +
+            return fqc::fail(FQ_E_UNSUPPORTED, W + fqc::dtype_name(cols[j].dtype) +
                                                    " column (scans over several columns need UInt64, Int64 or "
                                                    "Float64 columns)");
         if (need_data && cols[j].len > 0 && !cols[j].data)
-            return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: NULL column data");
+            return fqc::fail(FQ_E_INVALID, W + "NULL column data");
         if (((uintptr_t)cols[j].data) % 8)
-            return fqc::fail(FQ_E_INVALID, "fq_aggregate_columns: column not aligned to its element size");
+            return fqc::fail(FQ_E_INVALID, W + "column not aligned to its element size");
     }
     return FQ_OK;
 }

@@ -71,5 +71,11 @@ fq_status filter_project_blocks_enqueue(const fq_col *col, int64_t block_rows, c
                                         const fq_expr *values, int32_t n_out, void *const *d_out, int64_t *d_counts,
                                         uint64_t *h_result, uint64_t *d_result, void *d_ws, size_t ws_bytes,
                                         void *ev_start, void *ev_end, void *stream);
+// the same over the n_cols columns of fq_filter_project_blocks_columns
+fq_status filter_project_blocks_enqueue_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                                                const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                                void *const *d_out, int64_t *d_counts, uint64_t *h_result,
+                                                uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
+                                                void *ev_end, void *stream);
 fq_status filter_project_blocks_result(const uint64_t *h_result, int64_t *out_len);
 }  // namespace fqk

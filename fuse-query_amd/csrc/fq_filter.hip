@@ -479,9 +479,9 @@ struct ProjWs {
     int64_t ntiles;
 };
 
-ProjWs proj_ws(void *d_ws, int64_t n) {
+ProjWs proj_ws(void *d_ws, int64_t n, int n_cols = 1) {
     ProjWs w;
-    w.ntiles = (n + select_tile_rows() - 1) / select_tile_rows();
+    w.ntiles = (n + select_tile_rows(n_cols) - 1) / select_tile_rows(n_cols);
     w.total = (uint64_t *)d_ws;
     w.flags = (uint32_t *)(w.total + 1);
     w.ticket = (uint32_t *)(w.total + 2);
@@ -525,33 +525,66 @@ fq_status lower_projection(const fq_col *col, const fq_pred *pred, const fq_expr
     return FQ_OK;
 }
 
-}  // namespace
-}  // namespace fqk
-
-extern "C" {
-
-size_t fq_filter_project_workspace_bytes(int64_t len) {
-    const fqk::ProjWs w = fqk::proj_ws(nullptr, len < 0 ? 0 : len);
-    return (size_t)(2 + 16 + w.ntiles) * sizeof(uint64_t);
+// The same for the *_columns entry points over n_cols >= 2 checked columns
+// (one column goes through the single-column entry point): column references
+// are read from the steps and checked, FQ_OP_LOAD is accepted.  need_data =
+// false (fq_jit_prepare_project_columns): buffers may be NULL.
+fq_status lower_projection_cols(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *values,
+                                int32_t n_out, void *const *d_out, void *stream, bool need_data, const char *who,
+                                ProjLaunch &P) {
+    if (n_out < 0 || n_out > FQ_MAX_PROJECT || (n_out > 0 && (!values || (need_data && !d_out))))
+        return fqc::fail(FQ_E_INVALID, std::string(who) + ": bad output list");
+    P = ProjLaunch{};
+    P.col = cols[0].data;
+    P.n = cols[0].len;
+    P.stream = (hipStream_t)stream;
+    P.n_cols = n_cols;
+    for (int j = 0; j < n_cols; ++j) {
+        P.cols[j] = cols[j].data;
+        P.cdt[j] = cols[j].dtype;
+    }
+    fq_status s = lower_pred_cols(pred, P.cdt, n_cols, P.n, need_data, P.pred);
+    if (s != FQ_OK) return s;
+    P.n_out = n_out;
+    for (int j = 0; j < n_out; ++j) {
+        if (need_data && !d_out[j] && P.n > 0) return fqc::fail(FQ_E_INVALID, std::string(who) + ": NULL output");
+        int32_t dt = P.cdt[0];
+        s = lower_expr_cols(values[j], P.cdt, n_cols, P.vals[j], dt);
+        if (s != FQ_OK) return s;
+        P.chain[j] = values[j].n_steps > 0;
+        P.dtypes[j] = dt;
+        P.out[j] = d_out ? d_out[j] : nullptr;
+    }
+    return FQ_OK;
 }
 
-fq_status fq_filter_project(const fq_col *col, const fq_pred *pred, const fq_expr *values, int32_t n_out,
-                            void *const *d_out, int64_t *out_len, void *d_ws, size_t ws_bytes, void *stream) {
-    using namespace fqk;
-    if (!out_len) return fqc::fail(FQ_E_INVALID, "fq_filter_project: NULL out_len");
-    *out_len = 0;
-    ProjLaunch P;
-    fq_status s = lower_projection(col, pred, values, n_out, d_out, stream, P);
-    if (s != FQ_OK) return s;
-    if (n_out < 1) return fqc::fail(FQ_E_INVALID, "fq_filter_project: no outputs");
+// the column references of a one-column program through a *_columns entry
+// point (all must be 0)
+fq_status check_one_col_refs(const fq_col *col, const fq_pred *pred, const fq_expr *values, int32_t n_out) {
+    KProg kp;
+    KPred kd;
+    for (int j = 0; values && j < n_out && j < FQ_MAX_PROJECT; ++j) {
+        int32_t dt = col->dtype;
+        if (values[j].n_steps > 0) {
+            fq_status s = lower_expr_cols(values[j], &col->dtype, 1, kp, dt);
+            if (s != FQ_OK) return s;
+        }
+    }
+    return lower_pred_cols(pred, &col->dtype, 1, col->len, false, kd);
+}
+
+// fq_filter_project / fq_filter_project_columns after the lowering
+fq_status filter_project_run(int32_t col_dtype, const ProjLaunch &P, int64_t *out_len, void *d_ws, size_t ws_bytes) {
+    fq_status s;
+    const std::string who = P.n_cols > 1 ? "fq_filter_project_columns" : "fq_filter_project";
     if (!jit_project_available())
-        return fqc::fail(FQ_E_UNSUPPORTED, "fq_filter_project: hipRTC unavailable or the JIT is off");
-    if ((s = jit_project_prepare(col->dtype, P)) != FQ_OK) return s;
-    const int64_t n = col->len;
+        return fqc::fail(FQ_E_UNSUPPORTED, who + ": hipRTC unavailable or the JIT is off");
+    if ((s = jit_project_prepare(col_dtype, P)) != FQ_OK) return s;
+    const int64_t n = P.n;
     if (n == 0) return FQ_OK;
-    if (!d_ws || ws_bytes < fq_filter_project_workspace_bytes(n))
-        return fqc::fail(FQ_E_INVALID, "fq_filter_project: workspace too small");
-    const ProjWs w = proj_ws(d_ws, n);
+    const ProjWs w = proj_ws(d_ws, n, P.n_cols);
+    const size_t need = (size_t)(2 + 16 + w.ntiles) * sizeof(uint64_t);
+    if (!d_ws || ws_bytes < need) return fqc::fail(FQ_E_INVALID, who + ": workspace too small");
     hipStream_t st = P.stream;
     uint64_t local[2] = {0, 0};
     uint64_t *const pinned = fqc::host_staging();
@@ -559,12 +592,12 @@ fq_status fq_filter_project(const fq_col *col, const fq_pred *pred, const fq_exp
     host[0] = host[1] = 0;
     if (P.pred.kind == FQ_PRED_NONE) {
         FQ_HIP_TRY(hipMemsetAsync(w.flags, 0, 2 * sizeof(uint32_t), st));
-        if ((s = jit_project_map(col->dtype, P, w.flags + 1)) != FQ_OK) return s;
+        if ((s = jit_project_map(col_dtype, P, w.flags + 1)) != FQ_OK) return s;
         FQ_HIP_TRY(hipMemcpyAsync(&host[1], w.flags, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         host[0] = (uint64_t)n;
     } else {
-        FQ_HIP_TRY(hipMemsetAsync(d_ws, 0, fq_filter_project_workspace_bytes(n), st));
-        if ((s = jit_project_select(col->dtype, P, P.pred.kind == FQ_PRED_BITMAP ? P.pred.bitmap : nullptr, w.status,
+        FQ_HIP_TRY(hipMemsetAsync(d_ws, 0, need, st));
+        if ((s = jit_project_select(col_dtype, P, P.pred.kind == FQ_PRED_BITMAP ? P.pred.bitmap : nullptr, w.status,
                                     w.ticket, w.flags, w.total)) != FQ_OK)
             return s;
         FQ_HIP_TRY(hipMemcpyAsync(host, w.total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));  // total + flag words
@@ -577,35 +610,114 @@ fq_status fq_filter_project(const fq_col *col, const fq_pred *pred, const fq_exp
     return FQ_OK;
 }
 
+// fq_predicate_bitmap / fq_predicate_bitmap_columns after the lowering
+fq_status predicate_bitmap_run(int32_t col_dtype, ProjLaunch &P, uint64_t *d_bitmap, uint32_t *d_flag) {
+    fq_status s;
+    const std::string who = P.n_cols > 1 ? "fq_predicate_bitmap_columns" : "fq_predicate_bitmap";
+    if (P.pred.kind != FQ_PRED_EXPR && P.pred.kind != FQ_PRED_TREE)
+        return fqc::fail(FQ_E_INVALID, who + ": needs an FQ_PRED_EXPR or FQ_PRED_TREE predicate");
+    if (!jit_project_available())
+        return fqc::fail(FQ_E_UNSUPPORTED, who + ": hipRTC unavailable or the JIT is off");
+    P.n_out = 1;  // the module's shape needs one output; the bits kernel writes none
+    P.dtypes[0] = col_dtype;
+    if ((s = jit_project_prepare(col_dtype, P)) != FQ_OK) return s;
+    if (P.n == 0) return FQ_OK;
+    if (!d_bitmap || !d_flag) return fqc::fail(FQ_E_INVALID, who + ": NULL buffer");
+    FQ_HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), P.stream));
+    if ((s = jit_project_bits(col_dtype, P, d_bitmap, d_flag)) != FQ_OK) return s;
+    uint32_t local = 0;
+    uint64_t *const pinned = fqc::host_staging();
+    uint32_t *const h = pinned ? (uint32_t *)pinned : &local;
+    FQ_HIP_TRY(hipMemcpyAsync(h, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, P.stream));
+    FQ_HIP_TRY(hipStreamSynchronize(P.stream));
+    return flag_error(*h);
+}
+
+}  // namespace
+}  // namespace fqk
+
+extern "C" {
+
+size_t fq_filter_project_workspace_bytes(int64_t len) {
+    const fqk::ProjWs w = fqk::proj_ws(nullptr, len < 0 ? 0 : len);
+    return (size_t)(2 + 16 + w.ntiles) * sizeof(uint64_t);
+}
+
+size_t fq_filter_project_columns_workspace_bytes(int64_t len, int32_t n_cols) {
+    const fqk::ProjWs w = fqk::proj_ws(nullptr, len < 0 ? 0 : len, n_cols);
+    return (size_t)(2 + 16 + w.ntiles) * sizeof(uint64_t);
+}
+
+fq_status fq_filter_project(const fq_col *col, const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                            void *const *d_out, int64_t *out_len, void *d_ws, size_t ws_bytes, void *stream) {
+    using namespace fqk;
+    if (!out_len) return fqc::fail(FQ_E_INVALID, "fq_filter_project: NULL out_len");
+    *out_len = 0;
+    ProjLaunch P;
+    fq_status s = lower_projection(col, pred, values, n_out, d_out, stream, P);
+    if (s != FQ_OK) return s;
+    if (n_out < 1) return fqc::fail(FQ_E_INVALID, "fq_filter_project: no outputs");
+    return filter_project_run(col->dtype, P, out_len, d_ws, ws_bytes);
+}
+
+fq_status fq_filter_project_columns(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *values,
+                                    int32_t n_out, void *const *d_out, int64_t *out_len, void *d_ws, size_t ws_bytes,
+                                    void *stream) {
+    using namespace fqk;
+    if (!out_len) return fqc::fail(FQ_E_INVALID, "fq_filter_project_columns: NULL out_len");
+    *out_len = 0;
+    fq_status s = check_cols(cols, n_cols, true, "fq_filter_project_columns");
+    if (s != FQ_OK) return s;
+    if (n_cols == 1) {
+        if ((s = check_one_col_refs(cols, pred, values, n_out)) != FQ_OK) return s;
+        return fq_filter_project(cols, pred, values, n_out, d_out, out_len, d_ws, ws_bytes, stream);
+    }
+    ProjLaunch P;
+    s = lower_projection_cols(cols, n_cols, pred, values, n_out, d_out, stream, true, "fq_filter_project_columns", P);
+    if (s != FQ_OK) return s;
+    if (n_out < 1) return fqc::fail(FQ_E_INVALID, "fq_filter_project_columns: no outputs");
+    return filter_project_run(cols[0].dtype, P, out_len, d_ws, ws_bytes);
+}
+
 size_t fq_filter_project_blocks_workspace_bytes(void) { return 3 * sizeof(uint64_t); }  // total, flags, ticket
 
 }  // extern "C"
 
 namespace fqk {
 
-fq_status filter_project_blocks_enqueue(const fq_col *col, int64_t block_rows, const fq_pred *pred,
-                                        const fq_expr *values, int32_t n_out, void *const *d_out, int64_t *d_counts,
-                                        uint64_t *h_result, uint64_t *d_result, void *d_ws, size_t ws_bytes,
-                                        void *ev_start, void *ev_end, void *stream) {
+fq_status filter_project_blocks_enqueue_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                                                const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                                void *const *d_out, int64_t *d_counts, uint64_t *h_result,
+                                                uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
+                                                void *ev_end, void *stream) {
+    const std::string who = n_cols > 1 ? "fq_filter_project_blocks_columns" : "fq_filter_project_blocks";
     static_assert(FQ_PROJECT_MIN_BLOCK_ROWS == kProjectBlockTile, "the ABI's minimum block is the kernel's tile");
-    if (!h_result) return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks: NULL result words");
+    if (!h_result) return fqc::fail(FQ_E_INVALID, who + ": NULL result words");
     // a resident call's words are the caller's until the hand-off writes them
     // (the engine keeps a sentinel there to poll for)
     if (!d_result) h_result[0] = h_result[1] = 0;
     if (block_rows < FQ_PROJECT_MIN_BLOCK_ROWS)
-        return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks: block_rows below FQ_PROJECT_MIN_BLOCK_ROWS");
+        return fqc::fail(FQ_E_INVALID, who + ": block_rows below FQ_PROJECT_MIN_BLOCK_ROWS");
     ProjLaunch P;
-    fq_status s = lower_projection(col, pred, values, n_out, d_out, stream, P);
+    fq_status s;
+    if (n_cols == 1) {
+        s = lower_projection(cols, pred, values, n_out, d_out, stream, P);
+    } else {
+        if ((s = check_cols(cols, n_cols, true, "fq_filter_project_blocks_columns")) != FQ_OK) return s;
+        s = lower_projection_cols(cols, n_cols, pred, values, n_out, d_out, stream, true,
+                                  "fq_filter_project_blocks_columns", P);
+    }
     if (s != FQ_OK) return s;
-    if (n_out < 1) return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks: no outputs");
+    const fq_col *col = cols;
+    if (n_out < 1) return fqc::fail(FQ_E_INVALID, who + ": no outputs");
     if (!jit_project_available())
-        return fqc::fail(FQ_E_UNSUPPORTED, "fq_filter_project_blocks: hipRTC unavailable or the JIT is off");
+        return fqc::fail(FQ_E_UNSUPPORTED, who + ": hipRTC unavailable or the JIT is off");
     if ((s = jit_project_prepare(col->dtype, P)) != FQ_OK) return s;
     const int64_t n = col->len;
     if (n == 0) return FQ_OK;
-    if (!d_counts) return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks: NULL block counts");
+    if (!d_counts) return fqc::fail(FQ_E_INVALID, who + ": NULL block counts");
     if (!d_ws || ws_bytes < fq_filter_project_blocks_workspace_bytes())
-        return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks: workspace too small");
+        return fqc::fail(FQ_E_INVALID, who + ": workspace too small");
     uint64_t *const total = (uint64_t *)d_ws;
     uint32_t *const flags = (uint32_t *)(total + 1);
     uint32_t *const ticket = (uint32_t *)(total + 2);
@@ -639,6 +751,14 @@ fq_status filter_project_blocks_enqueue(const fq_col *col, int64_t block_rows, c
     return FQ_OK;
 }
 
+fq_status filter_project_blocks_enqueue(const fq_col *col, int64_t block_rows, const fq_pred *pred,
+                                        const fq_expr *values, int32_t n_out, void *const *d_out, int64_t *d_counts,
+                                        uint64_t *h_result, uint64_t *d_result, void *d_ws, size_t ws_bytes,
+                                        void *ev_start, void *ev_end, void *stream) {
+    return filter_project_blocks_enqueue_columns(col, 1, block_rows, pred, values, n_out, d_out, d_counts, h_result,
+                                                 d_result, d_ws, ws_bytes, ev_start, ev_end, stream);
+}
+
 fq_status filter_project_blocks_result(const uint64_t *h_result, int64_t *out_len) {
     if (!h_result || !out_len) return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks: NULL result");
     *out_len = 0;
@@ -667,6 +787,30 @@ fq_status fq_filter_project_blocks(const fq_col *col, int64_t block_rows, const 
     if (s != FQ_OK) return s;
     FQ_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return fqk::filter_project_blocks_result(host, out_len);
+}
+
+fq_status fq_filter_project_blocks_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                           const fq_expr *values, int32_t n_out, void *const *d_out,
+                                           int64_t *d_counts, int64_t *out_len, void *d_ws, size_t ws_bytes,
+                                           void *stream) {
+    using namespace fqk;
+    if (!out_len) return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks_columns: NULL out_len");
+    *out_len = 0;
+    fq_status s = check_cols(cols, n_cols, true, "fq_filter_project_blocks_columns");
+    if (s != FQ_OK) return s;
+    if (n_cols == 1) {
+        if ((s = check_one_col_refs(cols, pred, values, n_out)) != FQ_OK) return s;
+        return fq_filter_project_blocks(cols, block_rows, pred, values, n_out, d_out, d_counts, out_len, d_ws, ws_bytes,
+                                        stream);
+    }
+    uint64_t local[2] = {0, 0};
+    uint64_t *const pinned = fqc::host_staging();
+    uint64_t *const host = pinned ? pinned : local;  // kept rows, flag words
+    s = filter_project_blocks_enqueue_columns(cols, n_cols, block_rows, pred, values, n_out, d_out, d_counts, host,
+                                              nullptr, d_ws, ws_bytes, nullptr, nullptr, stream);
+    if (s != FQ_OK) return s;
+    FQ_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return filter_project_blocks_result(host, out_len);
 }
 
 size_t fq_blocks_compact_workspace_bytes(int64_t n_blocks) {
@@ -726,23 +870,52 @@ fq_status fq_predicate_bitmap(const fq_col *col, const fq_pred *pred, uint64_t *
     ProjLaunch P;
     fq_status s = lower_projection(col, pred, nullptr, 0, nullptr, stream, P);
     if (s != FQ_OK) return s;
-    if (P.pred.kind != FQ_PRED_EXPR && P.pred.kind != FQ_PRED_TREE)
-        return fqc::fail(FQ_E_INVALID, "fq_predicate_bitmap: needs an FQ_PRED_EXPR or FQ_PRED_TREE predicate");
-    if (!jit_project_available())
-        return fqc::fail(FQ_E_UNSUPPORTED, "fq_predicate_bitmap: hipRTC unavailable or the JIT is off");
-    P.n_out = 1;  // the module's shape needs one output; the bits kernel writes none
-    P.dtypes[0] = col->dtype;
-    if ((s = jit_project_prepare(col->dtype, P)) != FQ_OK) return s;
-    if (col->len == 0) return FQ_OK;
-    if (!d_bitmap || !d_flag) return fqc::fail(FQ_E_INVALID, "fq_predicate_bitmap: NULL buffer");
-    FQ_HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), P.stream));
-    if ((s = jit_project_bits(col->dtype, P, d_bitmap, d_flag)) != FQ_OK) return s;
-    uint32_t local = 0;
-    uint64_t *const pinned = fqc::host_staging();
-    uint32_t *const h = pinned ? (uint32_t *)pinned : &local;
-    FQ_HIP_TRY(hipMemcpyAsync(h, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, P.stream));
-    FQ_HIP_TRY(hipStreamSynchronize(P.stream));
-    return flag_error(*h);
+    return predicate_bitmap_run(col->dtype, P, d_bitmap, d_flag);
+}
+
+fq_status fq_predicate_bitmap_columns(const fq_col *cols, int32_t n_cols, const fq_pred *pred, uint64_t *d_bitmap,
+                                      uint32_t *d_flag, void *stream) {
+    using namespace fqk;
+    fq_status s = check_cols(cols, n_cols, true, "fq_predicate_bitmap_columns");
+    if (s != FQ_OK) return s;
+    if (n_cols == 1) {
+        if ((s = check_one_col_refs(cols, pred, nullptr, 0)) != FQ_OK) return s;
+        return fq_predicate_bitmap(cols, pred, d_bitmap, d_flag, stream);
+    }
+    ProjLaunch P;
+    s = lower_projection_cols(cols, n_cols, pred, nullptr, 0, nullptr, stream, true, "fq_predicate_bitmap_columns", P);
+    if (s != FQ_OK) return s;
+    return predicate_bitmap_run(cols[0].dtype, P, d_bitmap, d_flag);
+}
+
+fq_status fq_jit_prepare_project_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                         const fq_expr *values, int32_t n_out, int32_t *specialised) {
+    using namespace fqk;
+    if (specialised) *specialised = 0;
+    fq_status s = check_cols(cols, n_cols, false, "fq_jit_prepare_project_columns");
+    if (s != FQ_OK) return s;
+    if (block_rows != 0 && block_rows < FQ_PROJECT_MIN_BLOCK_ROWS)
+        return fqc::fail(FQ_E_INVALID, "fq_jit_prepare_project_columns: block_rows below FQ_PROJECT_MIN_BLOCK_ROWS");
+    if (n_out < 1 || n_out > FQ_MAX_PROJECT)
+        return fqc::fail(FQ_E_INVALID, "fq_jit_prepare_project_columns: n_out must be 1.." +
+                                           std::to_string(FQ_MAX_PROJECT) + ", got " + std::to_string(n_out));
+    // one column: the single-column module (column references all 0, ignored by its lowering)
+    ProjLaunch P;
+    if (n_cols == 1) {
+        if ((s = check_one_col_refs(cols, pred, values, n_out)) != FQ_OK) return s;
+        fq_col c0 = cols[0];
+        void *none[FQ_MAX_PROJECT] = {};
+        c0.len = 0;  // the shape only: no buffers needed
+        s = lower_projection(&c0, pred, values, n_out, none, nullptr, P);
+    } else {
+        s = lower_projection_cols(cols, n_cols, pred, values, n_out, nullptr, nullptr, false,
+                                  "fq_jit_prepare_project_columns", P);
+    }
+    if (s != FQ_OK) return s;
+    if (!jit_project_available()) return FQ_OK;  // the caller's unfused path answers
+    if ((s = jit_project_prepare(cols[0].dtype, P)) != FQ_OK) return s;
+    if (specialised) *specialised = 1;
+    return FQ_OK;
 }
 
 fq_status fq_filter_compact(const fq_col *in, const uint64_t *d_bitmap, void *d_out, int64_t *out_len,

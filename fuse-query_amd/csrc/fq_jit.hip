@@ -2415,6 +2415,21 @@ std::string proj_shape_key(const ProjLaunch &P, int32_t tin, int dev) {
             put(st.sdtype);
         }
     }
+    if (P.n_cols > 1) {  // several columns: their dtypes and every column reference
+        put(P.n_cols);
+        for (int j = 0; j < P.n_cols; ++j) put(P.cdt[j]);
+        auto cols = [&put](const KProg &p) {
+            for (int i = 0; i < p.n; ++i) put(p.s[i].col);
+        };
+        for (int j = 0; j < P.n_out; ++j)
+            if (P.chain[j]) cols(P.vals[j]);
+        put(P.pred.rhs_col);
+        cols(P.pred.lhs);
+        for (int l = 0; l < P.pred.n_leaves; ++l) {
+            put(P.pred.leaves[l].rhs_col);
+            cols(P.pred.leaves[l].lhs);
+        }
+    }
     return k;
 }
 
@@ -2455,9 +2470,166 @@ std::string proj_shape_key(const ProjLaunch &P, int32_t tin, int dev) {
 // mapping and pairs win: 0.7045 -> 0.6768 ms per 3.125e8-row block, 22.66 ->
 // 21.75 ms per p1 query, one process, 4 rounds (profiles/r06_i_p1_pairs_ab.json).
 // A tile that is ragged or not 16-byte aligned loads its pairs 8 bytes at a time.
-std::string gen_project_blocks_kernel(bool bitmap_pred) {
-    std::string s = "#define PB_ROWS " + std::to_string(fqc::knob(FQ_TUNE_SELECT_BLOCKS_ROWS)) + "\n#define PB_STAGE " +
-                    std::to_string(fqc::knob(FQ_TUNE_SELECT_BLOCKS_STAGE)) + "\n";
+//
+// Several columns (fq_filter_project_blocks_columns, gen_project_blocks_cols):
+// the same walk with the tile's rows of every column in registers, and
+// PB_ROWS = project_cols_rows(K) = 16, 16, 8 rows per thread (64, 96, 64 VGPRs
+// of row data; fq_scan.h has the measurement behind it).  The stage holds one
+// OUTPUT of the whole tile (32 KB for two and three columns, 16 KB for four,
+// whatever K and n_out): every lane evaluates output j for its own kept rows
+// from registers and writes it to the stage by in-tile rank; after a barrier
+// consecutive threads store it as 16-byte pairs.  One round, two barriers, per
+// output.  16-byte loads apply to a whole tile whose rows start on a 16-byte
+// boundary in every column; any other tile loads 8 bytes at a time.
+
+// "text with @ for the column number" -> the text once per column
+std::string for_cols(int K, const std::string &t, const char *sep = "") {
+    std::string o;
+    for (int j = 0; j < K; ++j) {
+        std::string u = t;
+        for (size_t p = 0; (p = u.find('@', p)) != std::string::npos;) u.replace(p, 1, std::to_string(j));
+        o += (j ? sep : "") + u;
+    }
+    return o;
+}
+
+// pb_copy and fq_jit_pblocks over K >= 2 columns (after the shared defines,
+// PbShared and pb_scan)
+std::string gen_project_blocks_cols(const ProjLaunch &P, int K) {
+    auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    std::string s = R"(// ranks [lo, hi) of the staged output go to out[d + rank].  al: every output
+// is 16-byte aligned -- row pairs as one 16-byte store each, the odd row at
+// either end alone; else one row per thread.
+__device__ __forceinline__ void pb_copy(const u64 *__restrict__ st, u32 lo, u32 hi, long long d, int al, int tid,
+                                        u64 *__restrict__ out) {
+    if (lo >= hi) return;
+    if (!al) {
+        for (u32 r = lo + tid; r < hi; r += PB_THREADS) __builtin_nontemporal_store(st[r], out + d + (long long)r);
+        return;
+    }
+    const long long p0 = d + lo, p1 = d + hi;
+    if ((p0 & 1) && tid == 0) __builtin_nontemporal_store(st[lo], out + p0);
+    if ((p1 & 1) && tid == 64) __builtin_nontemporal_store(st[hi - 1], out + p1 - 1);
+    for (long long q = ((p0 + 1) >> 1) + tid; q < (p1 >> 1); q += PB_THREADS)
+        __builtin_nontemporal_store(u64x2{st[2 * q - d], st[2 * q + 1 - d]}, ((u64x2 *)out) + q);
+}
+extern "C" __global__ void __launch_bounds__(PB_THREADS)
+fq_jit_pblocks()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, long long B, Consts c,
+    const u64 *__restrict__ bm, Outs o, long long *__restrict__ counts, u32 *__restrict__ fl,
+    unsigned long long *__restrict__ total, u32 *__restrict__ ticket, int al) {
+    __shared__ PbShared sh;
+    __shared__ u64 stage[PB_TILE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long nb = (n + B - 1) / B;
+    u64 kept = 0;  // the workgroup's kept rows
+    u32 pflags = 0, vflags = 0;
+    const u64 lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    int par = 0;
+    // one block per draw from the counter: the blocks in flight stay adjacent
+    __shared__ long long s_run;
+    for (;;) {
+        if (tid == 0) s_run = (long long)atomicAdd(ticket, 1u);
+        __syncthreads();
+        const long long run = s_run;
+        if (run >= nb) break;
+    const long long end = (run + 1) * B < n ? (run + 1) * B : n;
+    long long cur = run;  // the open block
+    u64 carry = 0;        // its kept rows so far
+    for (long long r0 = run * B; r0 < end; r0 += PB_TILE, par ^= 1) {
+        u64 *__restrict__ b0s = sh.b0[par];
+        u64 *__restrict__ b1s = sh.b1[par];
+        u32 *__restrict__ off = sh.off[par];
+        // 16-byte row-pair loads when the tile is whole and 16-byte aligned in every column
+)" + FOR("        TIn@ xa@[PB_NP], xb@[PB_NP];\n") +
+                    "        if (r0 + PB_TILE <= end && (((" + FOR("(unsigned long long)(col@ + r0)", " | ") +
+                    ") & 15ull) == 0ull)) {\n" + FOR("            const u32x4 *__restrict__ vp@ = (const u32x4 *)(col@ + r0);\n") +
+                    "#pragma unroll\n            for (int k = 0; k < PB_NP; ++k) {\n" +
+                    FOR("                const u32x4 raw@ = __builtin_nontemporal_load(vp@ + tid + k * PB_THREADS);\n") +
+                    FOR("                __builtin_memcpy(&xa@[k], &raw@, 8);\n"
+                        "                __builtin_memcpy(&xb@[k], ((const char *)&raw@) + 8, 8);\n") +
+                    "            }\n        } else {\n#pragma unroll\n            for (int k = 0; k < PB_NP; ++k) {\n"
+                    "                const long long row = r0 + 2 * (long long)(tid + k * PB_THREADS);\n" +
+                    FOR("                xa@[k] = row < end ? __builtin_nontemporal_load(col@ + row) : TIn@(0);\n"
+                        "                xb@[k] = row + 1 < end ? __builtin_nontemporal_load(col@ + row + 1) : TIn@(0);\n") +
+                    "            }\n        }\n"
+                    "#pragma unroll\n        for (int k = 0; k < PB_NP; ++k) {\n"
+                    "            const long long row = r0 + 2 * (long long)(tid + k * PB_THREADS);\n"
+                    "            const u32 live0 = row < end ? 1u : 0u, live1 = row + 1 < end ? 1u : 0u;\n";
+    s += P.pred.kind == FQ_PRED_BITMAP
+             ? std::string("            const bool p0 = live0 && ((bm[row >> 6] >> (row & 63)) & 1ull);\n"
+                           "            const bool p1 = live1 && ((bm[(row + 1) >> 6] >> ((row + 1) & 63)) & 1ull);\n"
+                           "            (void)c;\n")
+             : "            const bool p0 = fq_pred(" + FOR("xa@[k]", ", ") + ", c, pflags, live0) && live0;\n"
+               "            const bool p1 = fq_pred(" + FOR("xb@[k]", ", ") + ", c, pflags, live1) && live1;\n";
+    s += R"(            const u64 c0 = __ballot(p0), c1 = __ballot(p1);
+            if (lane == 0) {
+                b0s[k * PB_WAVES + wave] = c0;
+                b1s[k * PB_WAVES + wave] = c1;
+                off[k * PB_WAVES + wave] = (u32)(__popcll(c0) + __popcll(c1));
+            }
+        }
+        __syncthreads();
+        if (wave == 0) pb_scan(off, PB_NE, lane);
+        __syncthreads();
+        const u32 tot = off[PB_NE];
+        const long long bnd = (cur + 1) * B < n ? (cur + 1) * B : n;
+        const long long e = bnd - r0;
+        u32 re = tot;  // kept rows of the tile before the open block's edge
+        if (e < PB_TILE) {
+            const int g = (int)(e >> 7), pos = (int)(e & 127), h = pos >> 1;
+            const u64 m = (1ull << h) - 1ull;
+            re = off[g] + (u32)__popcll(b0s[g] & m) + (u32)__popcll(b1s[g] & m) +
+                 ((pos & 1) ? (u32)((b0s[g] >> h) & 1ull) : 0u);
+        }
+        const long long before = cur * B + (long long)carry;
+        const long long after = (cur + 1) * B - (long long)re;
+        // this lane's kept rows: in-tile rank of the pair's first kept row, and which of the two are kept
+        u32 rk[PB_NP], kk[PB_NP];
+#pragma unroll
+        for (int k = 0; k < PB_NP; ++k) {
+            const u64 c0 = b0s[k * PB_WAVES + wave], c1 = b1s[k * PB_WAVES + wave];
+            kk[k] = (u32)((c0 >> lane) & 1ull) | ((u32)((c1 >> lane) & 1ull) << 1);
+            rk[k] = off[k * PB_WAVES + wave] + (u32)__popcll(c0 & lt) + (u32)__popcll(c1 & lt);
+        }
+)";
+    for (int j = 0; j < P.n_out; ++j) {
+        const std::string J = std::to_string(j);
+        if (j) s += "        __syncthreads();  // the stage is read out\n";
+        s += "#pragma unroll\n        for (int k = 0; k < PB_NP; ++k) {\n"
+             "            if (kk[k] & 1u) stage[rk[k]] = __builtin_bit_cast(u64, fq_val" + J + "(" + FOR("xa@[k]", ", ") +
+             ", c, vflags, 1u));\n"
+             "            if (kk[k] & 2u) stage[rk[k] + (kk[k] & 1u)] = __builtin_bit_cast(u64, fq_val" + J + "(" +
+             FOR("xb@[k]", ", ") + ", c, vflags, 1u));\n"
+             "        }\n        __syncthreads();\n"
+             "        pb_copy(stage, 0u, re, before, al, tid, (u64 *)o.p[" + J + "]);\n"
+             "        pb_copy(stage, re, tot, after, al, tid, (u64 *)o.p[" + J + "]);\n";
+    }
+    s += R"PB(
+        kept += tot;
+        if (e <= PB_TILE) {
+            if (tid == 0) counts[cur] = (long long)(carry + re);
+            carry = tot - re;
+            ++cur;
+        } else {
+            carry += tot;
+        }
+    }
+    }
+    pflags = wave_or(pflags);
+    vflags = wave_or(vflags);
+    if (lane == 0 && pflags) atomicOr(fl, pflags);
+    if (lane == 0 && vflags) atomicOr(fl + 1, vflags);
+    if (tid == 0 && kept) atomicAdd(total, (unsigned long long)kept);
+}
+)PB";
+    return s;
+}
+
+std::string gen_project_blocks_kernel(const ProjLaunch &P, int K) {
+    const bool bitmap_pred = P.pred.kind == FQ_PRED_BITMAP;
+    // several columns: project_cols_rows(K) rows per thread and a whole-tile stage of one output
+    std::string s = "#define PB_ROWS " + std::to_string(K > 1 ? project_cols_rows(K) : fqc::knob(FQ_TUNE_SELECT_BLOCKS_ROWS)) +
+                    "\n#define PB_STAGE " + std::to_string(K > 1 ? 1 : fqc::knob(FQ_TUNE_SELECT_BLOCKS_STAGE)) + "\n";
     s += R"(
 #define PB_THREADS 256
 #define PB_WAVES (PB_THREADS / 64)
@@ -2494,7 +2666,9 @@ __device__ __forceinline__ void pb_scan(u32 *__restrict__ off, int ng, int lane)
     }
     if (lane == 63) off[ng] = incl;
 }
-#if PB_STAGE
+)";
+    if (K > 1) return s + gen_project_blocks_cols(P, K);
+    s += R"(#if PB_STAGE
 // PB_STAGE: the tile's kept rows staged in LDS by in-tile rank, then written
 // out by consecutive threads: ranks [lo, hi) go to output rows d + rank, rank
 // r in st[r - base].  al: every output is 16-byte aligned -- row pairs as one
@@ -2650,33 +2824,213 @@ fq_jit_pblocks(const TIn *__restrict__ col, long long n, long long B, Consts c,
     return s;
 }
 
+// The row loops of fq_jit_pbits, fq_jit_pselect and fq_jit_pmap over K >= 2
+// columns (gen_project_source has the single-column text): the same rows of
+// every column loaded together, the rows per lane in flight divided by K.
+std::string gen_project_bits_cols(int K) {
+    auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    const std::string W = std::to_string(std::max(1, 8 / K));  // 64-row words per wave per step
+    return "\nextern \"C\" __global__ void __launch_bounds__(256)\nfq_jit_pbits(" +
+           FOR("const TIn@ *__restrict__ col@, ") +
+           "long long n, Consts c, u64 *__restrict__ bm, u32 *__restrict__ fl) {\n"
+           "    const int lane = threadIdx.x & 63;\n"
+           "    const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;\n"
+           "    const long long W = ((long long)gridDim.x * 256) >> 6;\n"
+           "    const long long nwords = (n + 63) >> 6;\n"
+           "    u32 flags = 0;\n"
+           "    for (long long w0 = wave * " + W + "; w0 < nwords; w0 += W * " + W + ") {\n" +
+           FOR("        TIn@ x@[" + W + "];\n") +
+           "#pragma unroll\n        for (int k = 0; k < " + W + "; ++k) {\n"
+           "            const long long r = (w0 + k) * 64 + lane;\n" +
+           FOR("            x@[k] = r < n ? __builtin_nontemporal_load(col@ + r) : TIn@(0);\n") +
+           "        }\n        u64 mine = 0;\n"
+           "#pragma unroll\n        for (int k = 0; k < " + W + "; ++k) {\n"
+           "            const long long r = (w0 + k) * 64 + lane;\n"
+           "            const u32 live = r < n ? 1u : 0u;\n"
+           "            const bool pass = fq_pred(" + FOR("x@[k]", ", ") + ", c, flags, live) && live;\n"
+           "            const u64 word = __ballot(pass);\n"
+           "            if (lane == k) mine = word;\n"
+           "        }\n"
+           "        if (lane < " + W + " && w0 + lane < nwords) bm[w0 + lane] = mine;\n"
+           "    }\n"
+           "    flags = wave_or(flags);\n"
+           "    if (lane == 0 && flags) atomicOr(fl, flags);\n}\n";
+}
+
+// PsCtx, ps_ticket, ps_load and the head of ps_pred
+std::string gen_project_select_head_cols(int K) {
+    auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    return "struct PsCtx {\n" + FOR("    const TIn@ *__restrict__ col@;\n") +
+           "    long long n, ntiles;\n"
+           "    const u64 *__restrict__ bm;\n"
+           "    u64 *__restrict__ status;\n"
+           "    u32 *__restrict__ ticket;\n"
+           "};\n"
+           "// the next tile for this workgroup (thread 0 only); >= ntiles when none is left\n"
+           "__device__ __forceinline__ long long ps_ticket(const PsCtx &X) { return atomicAdd(X.ticket, 1u); }\n"
+           "__device__ __forceinline__ void ps_load(const PsCtx &X, long long t, " + FOR("TIn@ (&x@)[PS_ROWS]", ", ") + ") {\n"
+           "    const long long r0 = t * PS_TILE + threadIdx.x;\n"
+           "    if (t * PS_TILE + PS_TILE <= X.n) {\n"
+           "#pragma unroll\n        for (int k = 0; k < PS_ROWS; ++k) {\n" +
+           FOR("            x@[k] = __builtin_nontemporal_load(X.col@ + r0 + k * PS_THREADS);\n") +
+           "        }\n    } else {\n"
+           "#pragma unroll\n        for (int k = 0; k < PS_ROWS; ++k) {\n"
+           "            const long long row = r0 + k * PS_THREADS;\n" +
+           FOR("            x@[k] = row < X.n ? __builtin_nontemporal_load(X.col@ + row) : TIn@(0);\n") +
+           "        }\n    }\n}\n"
+           "// tile t's predicate into slot S: ballots, in-tile offsets, aggregate; wave 0\n"
+           "// publishes A (tile 0: P, base 0).  Contains one barrier.\n"
+           "template <int S>\n"
+           "__device__ __forceinline__ void ps_pred(const PsCtx &X, const Consts &c, PsShared &sh, long long t,\n"
+           "                                        " + FOR("const TIn@ (&x@)[PS_ROWS], ") + "u32 &pflags) {\n";
+}
+
+// ps_single, fq_jit_pselect and fq_jit_pmap
+std::string gen_project_select_tail_cols(int K) {
+    auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    const std::string XA = FOR("x@", ", ");
+    const std::string U = std::to_string(std::max(1, 4 / K));  // 16-byte pairs per lane per column in flight (pmap)
+    std::string s =
+        "// one tile: draw, load, predicate, look back, store; false when none is left\n"
+        "template <int S>\n"
+        "__device__ __forceinline__ bool ps_single(PsCtx &X, const Consts &c, const Outs &o, u64 *__restrict__ total,\n"
+        "                                          PsShared &sh, " + FOR("TIn@ (&x@)[PS_ROWS], ") + "u32 &pflags, u32 &vflags) {\n"
+        "    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;\n"
+        "    if (tid == 0) sh.tk = ps_ticket(X);\n"
+        "    __syncthreads();\n"
+        "    const long long t = sh.tk;\n"
+        "    if (t >= X.ntiles) return false;\n"
+        "    ps_load(X, t, " + XA + ");\n"
+        "    ps_pred<S>(X, c, sh, t, " + XA + ", pflags);\n";
+    s += R"(    if (wave == 0) {
+        u64 excl = 0;
+        if (t != 0) {
+            long long j = t - 1;
+            unsigned polls = 0;
+            while (!ps_poll(X, j, excl, polls, vflags)) {
+#if PS_SLEEP > 0
+                __builtin_amdgcn_s_sleep(PS_SLEEP);
+#endif
+            }
+        }
+        if (lane == 0) {
+            sh.base[S] = excl;
+            if (t != 0) __hip_atomic_store(X.status + t, PS_P | (excl + sh.agg[S]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    const u64 base = sh.base[S];
+    const u64 lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+#pragma unroll
+    for (int k = 0; k < PS_ROWS; ++k) {
+        const u64 b = sh.bal[S][k][wave];
+        if ((b >> lane) & 1ull)
+            fq_put()" + FOR("x@[k]", ", ") + R"(, c, vflags, 1u, o, (long long)(base + sh.off[S][k * PS_WAVES + wave] + (u32)__popcll(b & lt)));
+    }
+    if (t == X.ntiles - 1 && tid == 0) *total = base + sh.agg[S];
+    return true;
+}
+extern "C" __global__ void __launch_bounds__(PS_THREADS)
+fq_jit_pselect()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, Consts c, const u64 *__restrict__ bm, Outs o,
+               u64 *__restrict__ status, u32 *__restrict__ ticket, u32 *__restrict__ fl, u64 *__restrict__ total) {
+    __shared__ PsShared sh;
+    PsCtx X;
+)" + FOR("    X.col@ = col@;\n") + R"(    X.n = n;
+    X.ntiles = (n + PS_TILE - 1) / PS_TILE;
+    X.bm = bm;
+    X.status = status;
+    X.ticket = ticket;
+    u32 pflags = 0, vflags = 0;
+    {
+)" + FOR("        TIn@ x@[PS_ROWS];\n") +
+         "        while (ps_single<0>(X, c, o, total, sh, " + XA + ", pflags, vflags) && ps_single<1>(X, c, o, total, sh, " + XA +
+         ", pflags, vflags)) {\n" + R"(        }
+    }
+    pflags = wave_or(pflags);
+    vflags = wave_or(vflags);
+    if ((threadIdx.x & 63) == 0 && pflags) atomicOr(fl, pflags);
+    if ((threadIdx.x & 63) == 0 && vflags) atomicOr(fl + 1, vflags);
+}
+
+// every row: 16-byte loads and stores of row pairs when every column and every
+// output are 16-byte aligned (aligned != 0), else 8-byte rows
+extern "C" __global__ void __launch_bounds__(256)
+fq_jit_pmap()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, Consts c, Outs o, int aligned, u32 *__restrict__ fl) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long T = (long long)gridDim.x * 256;
+    u32 flags = 0;
+    long long done = 0;
+    if (aligned) {
+        const long long npair = n >> 1;
+)" + FOR("        const u64x2 *__restrict__ vp@ = (const u64x2 *)col@;\n") +
+         "        for (long long p0 = g; p0 < npair; p0 += " + U + " * T) {\n" + FOR("            u64x2 raw@[" + U + "];\n") +
+         "#pragma unroll\n            for (int k = 0; k < " + U + "; ++k) {\n"
+         "                const long long p = p0 + (long long)k * T;\n"
+         "                if (p < npair) { " + FOR("raw@[k] = __builtin_nontemporal_load(vp@ + p); ") + "}\n"
+         "                else { " + FOR("raw@[k] = u64x2{0, 0}; ") + "}\n"
+         "            }\n"
+         "#pragma unroll\n            for (int k = 0; k < " + U + "; ++k) {\n"
+         "                const long long p = p0 + (long long)k * T;\n"
+         "                if (p < npair)\n"
+         "                    fq_put2(" + FOR("__builtin_bit_cast(TIn@, (u64)raw@[k].x)", ", ") + ",\n"
+         "                            " + FOR("__builtin_bit_cast(TIn@, (u64)raw@[k].y)", ", ") + ", c, flags, o, p);\n"
+         "            }\n        }\n        done = npair * 2;\n    }\n"
+         "    for (long long i = done + g; i < n; i += T) fq_put(" + FOR("col@[i]", ", ") + ", c, flags, 1u, o, i);\n"
+         "    flags = wave_or(flags);\n"
+         "    if ((threadIdx.x & 63) == 0 && flags) atomicOr(fl, flags);\n}\n";
+    return s;
+}
+
 bool gen_project_source(const ProjLaunch &P, int32_t tin, int dev, Gen &g, std::string &src) {
     const char *TIn = ctype(tin);
     if (!TIn || P.n_out < 1 || P.n_out > FQ_MAX_PROJECT) return false;
     const int32_t pk = P.pred.kind;
+    // several columns: every per-row function takes x0 .. x{K-1} (as gen_source)
+    const int K = P.n_cols > 1 ? P.n_cols : 0;
+    auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    std::string XP = "TIn x", XA = "x";  // the row's elements as parameters / as arguments
+    if (K) {
+        g.n_cols = K;
+        for (int j = 0; j < K; ++j) {
+            if (!ctype(P.cdt[j])) return false;
+            g.cdt[j] = P.cdt[j];
+        }
+        XP = FOR("TIn@ x@", ", ");
+        XA = FOR("x@", ", ");
+    }
     std::string pred_body;
     const bool expr_pred = pk == FQ_PRED_EXPR || pk == FQ_PRED_TREE;
     if (expr_pred && !emit_pred_body(g, P.pred, tin, pred_body)) return false;
     src = kCommon;
-    src += "typedef " + std::string(TIn) + " TIn;\n";
+    if (K) {
+        for (int j = 0; j < K; ++j) src += "typedef " + std::string(ctype(P.cdt[j])) + " TIn" + std::to_string(j) + ";\n";
+    } else {
+        src += "typedef " + std::string(TIn) + " TIn;\n";
+    }
     src += "struct Step { u64 c, m, s; };\nstruct Consts { u64 rhs; Step p[" + std::to_string(kSteps) + "], v[" +
            std::to_string(FQ_MAX_PROJECT) + "][" + std::to_string(kSteps) + "]; u64 rl[" +
            std::to_string(FQ_MAX_PRED_LEAVES) + "]; Step pl[" + std::to_string(FQ_MAX_PRED_LEAVES) + "][" +
            std::to_string(kSteps) + "]; };\n";
     src += "struct Outs { void *p[" + std::to_string(FQ_MAX_PROJECT) + "]; };\n";
-    src += "#define PS_ROWS " + std::to_string(select_rows_per_thread()) + "\n#define PS_THREADS " +
+    src += "#define PS_ROWS " + std::to_string(project_cols_rows(K)) + "\n#define PS_THREADS " +
            std::to_string(select_threads()) + "\n#define PS_SLEEP " + std::to_string(select_sleep()) +
            "\n";
     src += "typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));\n";
-    src += "__device__ __forceinline__ bool fq_pred(TIn x, const Consts &c, u32 &flags, u32 live) {\n";
-    src += expr_pred ? pred_body : "    (void)x; (void)c; (void)flags; (void)live;\n    return true;\n";
+    src += "__device__ __forceinline__ bool fq_pred(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n";
+    src += expr_pred ? pred_body
+                     : (K ? FOR("(void)x@; ") : std::string("(void)x; ")).insert(0, "    ") +
+                           "(void)c; (void)flags; (void)live;\n    return true;\n";
     src += "}\n";
     // every output: its value function and its 64-bit store
-    std::string put_all = "__device__ __forceinline__ void fq_put(TIn x, const Consts &c, u32 &flags, u32 live, const Outs &o,\n"
+    std::string put_all = "__device__ __forceinline__ void fq_put(" + XP + ", const Consts &c, u32 &flags, u32 live, const Outs &o,\n"
                           "                                       long long pos) {\n";
-    std::string put_nt = "__device__ __forceinline__ void fq_put_nt(TIn x, const Consts &c, u32 &flags, u32 live, const Outs &o,\n"
+    std::string put_nt = "__device__ __forceinline__ void fq_put_nt(" + XP + ", const Consts &c, u32 &flags, u32 live, const Outs &o,\n"
                          "                                          long long pos) {\n";
-    std::string vals_pair = "__device__ __forceinline__ void fq_put2(TIn x0, TIn x1, const Consts &c, u32 &flags, const Outs &o,\n"
+    // the two rows of a pair: (x0, x1), or over several columns (a0 .. a{K-1}, b0 .. b{K-1})
+    const std::string PA = K ? FOR("a@", ", ") : "x0", PB = K ? FOR("b@", ", ") : "x1";
+    std::string vals_pair = "__device__ __forceinline__ void fq_put2(" +
+                            (K ? FOR("TIn@ a@", ", ") + ", " + FOR("TIn@ b@", ", ") : std::string("TIn x0, TIn x1")) +
+                            ", const Consts &c, u32 &flags, const Outs &o,\n"
                             "                                        long long pair) {\n";
     for (int j = 0; j < P.n_out; ++j) {
         const char *V = ctype(P.dtypes[j]);
@@ -2685,13 +3039,14 @@ bool gen_project_source(const ProjLaunch &P, int32_t tin, int dev, Gen &g, std::
         const std::string prefix = "v[" + std::to_string(j) + "]";
         emit_value_body(g, P.chain[j] ? &P.vals[j] : nullptr, tin, P.dtypes[j], prefix.c_str(), V, body);
         const std::string J = std::to_string(j);
-        src += std::string("__device__ __forceinline__ ") + V + " fq_val" + J + "(TIn x, const Consts &c, u32 &flags, u32 live) {\n" +
+        src += std::string("__device__ __forceinline__ ") + V + " fq_val" + J + "(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n" +
                "    (void)live;\n" + body + "}\n";
-        put_all += std::string("    ((") + V + " *)o.p[" + J + "])[pos] = fq_val" + J + "(x, c, flags, live);\n";
-        put_nt += std::string("    __builtin_nontemporal_store(fq_val") + J + "(x, c, flags, live), ((" + V + " *)o.p[" + J + "]) + pos);\n";
-        vals_pair += std::string("    { const ") + V + " a = fq_val" + J + "(x0, c, flags, 1u), b = fq_val" + J +
-                     "(x1, c, flags, 1u);\n      __builtin_nontemporal_store(u64x2{__builtin_bit_cast(u64, a), "
-                     "__builtin_bit_cast(u64, b)}, ((u64x2 *)o.p[" + J + "]) + pair); }\n";
+        put_all += std::string("    ((") + V + " *)o.p[" + J + "])[pos] = fq_val" + J + "(" + XA + ", c, flags, live);\n";
+        put_nt += std::string("    __builtin_nontemporal_store(fq_val") + J + "(" + XA + ", c, flags, live), ((" + V + " *)o.p[" + J + "]) + pos);\n";
+        vals_pair += std::string("    { const ") + V + (K ? " va" : " a") + " = fq_val" + J + "(" + PA + ", c, flags, 1u), " +
+                     (K ? "vb" : "b") + " = fq_val" + J + "(" + PB +
+                     ", c, flags, 1u);\n      __builtin_nontemporal_store(u64x2{__builtin_bit_cast(u64, " + (K ? "va" : "a") +
+                     "), __builtin_bit_cast(u64, " + (K ? "vb" : "b") + ")}, ((u64x2 *)o.p[" + J + "]) + pair); }\n";
     }
     src += put_all + "}\n" + put_nt + "}\n" + vals_pair + "}\n";
     src += R"(
@@ -2700,7 +3055,9 @@ __device__ __forceinline__ u32 wave_or(u32 f) {
     for (int off = 32; off > 0; off >>= 1) f |= (u32)__shfl_xor((int)f, off, 64);
     return f;
 }
-
+)";
+    if (K) src += gen_project_bits_cols(K);
+    else src += R"(
 extern "C" __global__ void __launch_bounds__(256)
 fq_jit_pbits(const TIn *__restrict__ col, long long n, Consts c, u64 *__restrict__ bm, u32 *__restrict__ fl) {
     const int lane = threadIdx.x & 63;
@@ -2729,7 +3086,8 @@ fq_jit_pbits(const TIn *__restrict__ col, long long n, Consts c, u64 *__restrict
     flags = wave_or(flags);
     if (lane == 0 && flags) atomicOr(fl, flags);
 }
-
+)";
+    src += R"(
 // Single pass over the column (decoupled look-back).  A workgroup draws a
 // tile of PS_TILE rows (lane-consecutive 8-byte rows, PS_ROWS per lane in
 // flight), evaluates the predicate (one ballot per 64 rows, kept in LDS),
@@ -2788,7 +3146,9 @@ struct PsShared {
     u64 base[2], agg[2];
     long long tk;  // ticket drawn (broadcast)
 };
-struct PsCtx {
+)";
+    if (K) src += gen_project_select_head_cols(K);
+    else src += R"(struct PsCtx {
     const TIn *__restrict__ col;
     long long n, ntiles;
     const u64 *__restrict__ bm;
@@ -2815,15 +3175,18 @@ __device__ __forceinline__ void ps_load(const PsCtx &X, long long t, TIn (&x)[PS
 template <int S>
 __device__ __forceinline__ void ps_pred(const PsCtx &X, const Consts &c, PsShared &sh, long long t, const TIn (&x)[PS_ROWS],
                                         u32 &pflags) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+)";
+    src += R"(    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long r0 = t * PS_TILE;
 #pragma unroll
     for (int k = 0; k < PS_ROWS; ++k) {
         const long long row = r0 + k * PS_THREADS + tid;
         const u32 live = row < X.n ? 1u : 0u;
 )" + std::string(P.pred.kind == FQ_PRED_BITMAP
-                     ? "        const bool p = live && ((X.bm[row >> 6] >> (row & 63)) & 1ull);\n        (void)c;\n        (void)x;\n        (void)pflags;\n"
-                     : "        const bool p = fq_pred(x[k], c, pflags, live) && live;\n") + R"(
+                     ? "        const bool p = live && ((X.bm[row >> 6] >> (row & 63)) & 1ull);\n        (void)c;\n" +
+                           (K ? FOR("        (void)x@;\n") : std::string("        (void)x;\n")) + "        (void)pflags;\n"
+                     : "        const bool p = fq_pred(" + (K ? FOR("x@[k]", ", ") : std::string("x[k]")) +
+                           ", c, pflags, live) && live;\n") + R"(
         const u64 b = __ballot(p);
         if (lane == 0) {
             sh.bal[S][k][wave] = b;
@@ -2905,7 +3268,13 @@ __device__ __forceinline__ bool ps_poll(const PsCtx &X, long long &j, u64 &excl,
         j -= 64 * PS_LBW;
     }
 }
-// one tile: draw, load, predicate, look back, store; false when none is left
+)";
+    if (K) {
+        src += gen_project_select_tail_cols(K);
+        src += gen_project_blocks_kernel(P, K);
+        return true;
+    }
+    src += R"(// one tile: draw, load, predicate, look back, store; false when none is left
 template <int S>
 __device__ __forceinline__ bool ps_single(PsCtx &X, const Consts &c, const Outs &o, u64 *__restrict__ total,
                                           PsShared &sh, TIn (&x)[PS_ROWS], u32 &pflags, u32 &vflags) {
@@ -2999,7 +3368,7 @@ fq_jit_pmap(const TIn *__restrict__ col, long long n, Consts c, Outs o, int alig
     if ((threadIdx.x & 63) == 0 && flags) atomicOr(fl, flags);
 }
 )";
-    src += gen_project_blocks_kernel(P.pred.kind == FQ_PRED_BITMAP);
+    src += gen_project_blocks_kernel(P, K);
     return true;
 }
 
@@ -3361,6 +3730,26 @@ fq_status get_proj_kernels(int32_t col_dtype, const ProjLaunch &P, ProjKernels *
     return FQ_OK;
 }
 
+// The kernels' leading arguments: the column pointer, or the n_cols pointers of
+// a *_columns call; the caller appends the rest.
+struct ProjArgs {
+    const void *cols[FQ_MAX_SCAN_COLS];
+    void *v[FQ_MAX_SCAN_COLS + 12];
+    int n = 0;
+    explicit ProjArgs(const ProjLaunch &P) {
+        const int K = P.n_cols > 1 ? P.n_cols : 1;
+        for (int j = 0; j < K; ++j) {
+            cols[j] = P.n_cols > 1 ? P.cols[j] : P.col;
+            v[n++] = &cols[j];
+        }
+    }
+    template <typename... A>
+    void **with(A *...rest) {
+        ((v[n++] = (void *)rest), ...);
+        return v;
+    }
+};
+
 int proj_grid(int64_t units, int per_wg) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -3385,11 +3774,13 @@ fq_status jit_project_bits(int32_t col_dtype, const ProjLaunch &P, uint64_t *d_b
     if (s != FQ_OK || !k.bits || P.n == 0) return s;
     HostProjConsts hc;
     pack_proj_consts(P, hc);
-    const void *col = P.col;
     long long n = P.n;
     const int64_t nwords = (P.n + 63) / 64;
-    void *args[] = {&col, &n, &hc, &d_bitmap, &d_flag};
-    FQ_HIP_TRY(hipModuleLaunchKernel(k.bits, (unsigned)proj_grid(nwords, 4 * 8), 1, 1, kThreads, 1, 1, 0, P.stream,
+    ProjArgs pa(P);
+    void **args = pa.with(&n, &hc, &d_bitmap, &d_flag);
+    // a wave takes 8 words per step over one column, 8 / K over K (gen_project_bits_cols)
+    const int wave_words = P.n_cols > 1 ? std::max(1, 8 / P.n_cols) : 8;
+    FQ_HIP_TRY(hipModuleLaunchKernel(k.bits, (unsigned)proj_grid(nwords, 4 * wave_words), 1, 1, kThreads, 1, 1, 0, P.stream,
                                      args, nullptr));
     g_jit_launches += 1;
     return FQ_OK;
@@ -3406,10 +3797,10 @@ fq_status jit_project_select(int32_t col_dtype, const ProjLaunch &P, const uint6
         void *p[FQ_MAX_PROJECT];
     } outs;
     for (int j = 0; j < FQ_MAX_PROJECT; ++j) outs.p[j] = j < P.n_out ? P.out[j] : nullptr;
-    const void *col = P.col;
     long long n = P.n;
-    const int64_t ntiles = (P.n + select_tile_rows() - 1) / select_tile_rows();
-    void *args[] = {&col, &n, &hc, &d_bitmap, &outs, &status, &ticket, &d_flags, &d_total};
+    const int64_t ntiles = (P.n + select_tile_rows(P.n_cols) - 1) / select_tile_rows(P.n_cols);
+    ProjArgs pa(P);
+    void **args = pa.with(&n, &hc, &d_bitmap, &outs, &status, &ticket, &d_flags, &d_total);
     const int wg_per_cu = (int)fqc::knob(FQ_TUNE_SELECT_WG_PER_CU);
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -3452,13 +3843,13 @@ fq_status jit_project_blocks(int32_t col_dtype, const ProjLaunch &P, int64_t blo
         void *p[FQ_MAX_PROJECT];
     } outs;
     for (int j = 0; j < FQ_MAX_PROJECT; ++j) outs.p[j] = j < P.n_out ? P.out[j] : nullptr;
-    const void *col = P.col;
     // a block longer than the column is the whole column (one block; keeps n + B in range)
     long long n = P.n, B = std::min<int64_t>(block_rows, P.n);
     const int64_t nb = (P.n + B - 1) / B;
     int al = 1;  // PB_STAGE row pairs need 16-byte aligned outputs
     for (int j = 0; j < P.n_out; ++j) al &= ((uintptr_t)P.out[j] & 15) == 0;
-    void *args[] = {&col, &n, &B, &hc, &d_bitmap, &outs, &d_counts, &d_flags, &d_total, &d_ticket, &al};
+    ProjArgs pa(P);
+    void **args = pa.with(&n, &B, &hc, &d_bitmap, &outs, &d_counts, &d_flags, &d_total, &d_ticket, &al);
     hipFunction_t fn = k.blocks;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -3499,13 +3890,15 @@ fq_status jit_project_map(int32_t col_dtype, const ProjLaunch &P, uint32_t *d_fl
         void *p[FQ_MAX_PROJECT];
     } outs;
     int aligned = ((uintptr_t)P.col & 15u) == 0;
+    for (int j = 1; j < P.n_cols; ++j)
+        if ((uintptr_t)P.cols[j] & 15u) aligned = 0;
     for (int j = 0; j < FQ_MAX_PROJECT; ++j) {
         outs.p[j] = j < P.n_out ? P.out[j] : nullptr;
         if (j < P.n_out && ((uintptr_t)P.out[j] & 15u)) aligned = 0;
     }
-    const void *col = P.col;
     long long n = P.n;
-    void *args[] = {&col, &n, &hc, &outs, &aligned, &d_flag};
+    ProjArgs pa(P);
+    void **args = pa.with(&n, &hc, &outs, &aligned, &d_flag);
     FQ_HIP_TRY(hipModuleLaunchKernel(k.map, (unsigned)proj_grid(n / 2, kThreads * 4), 1, 1, kThreads, 1, 1, 0, P.stream,
                                      args, nullptr));
     g_jit_launches += 1;

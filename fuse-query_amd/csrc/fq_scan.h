@@ -48,6 +48,9 @@ fq_status lower_pred(const fq_pred *pred, int32_t col_dtype, int64_t len, bool n
 fq_status lower_expr_cols(const fq_expr &e, const int32_t *cdt, int n_cols, KProg &out, int32_t &res_dtype);
 fq_status lower_pred_cols(const fq_pred *pred, const int32_t *cdt, int n_cols, int64_t len, bool need_data,
                           KPred &out);
+// Argument checks of the *_columns entry points: 1..FQ_MAX_SCAN_COLS columns of
+// equal len, each UINT64 / INT64 / FLOAT64 (`who` names the caller in the messages).
+fq_status check_cols(const fq_col *cols, int32_t n_cols, bool need_data, const char *who = "fq_aggregate_columns");
 
 // Flat scan over K >= 2 columns: 16-byte vectors per lane per column in a
 // tile, the next tile's as many in flight.  One column holds 2 x 4; K columns
@@ -174,7 +177,20 @@ struct ProjLaunch {
     int32_t dtypes[FQ_MAX_PROJECT];
     void *out[FQ_MAX_PROJECT];
     hipStream_t stream;
+    // the *_columns entry points with more than one column (else n_cols == 0):
+    // the columns and their dtypes, as in Launch
+    int n_cols;
+    const void *cols[FQ_MAX_SCAN_COLS];
+    int32_t cdt[FQ_MAX_SCAN_COLS];
 };
+
+// Rows per thread per tile of the look-back and block-stream kernels over K
+// columns: 16, 16, 8 for K = 2, 3, 4 (64, 96, 64 VGPRs of row data; one column
+// holds 32 rows, 64 VGPRs).  Dividing 32 by K and rounding down (8 at K = 3)
+// kept the registers where the single-column kernels have them but measured
+// 9-17 % slower than 16: half the barriers and status words per row win
+// (profiles/r08_project_columns_rows_ab.json).
+constexpr int project_cols_rows(int n_cols) { return n_cols <= 1 ? 32 : (n_cols <= 3 ? 16 : 8); }
 
 // predicate -> LSB-first bitmap words; predicate errors OR-ed into *d_flag
 fq_status jit_project_bits(int32_t col_dtype, const ProjLaunch &P, uint64_t *d_bitmap, uint32_t *d_flag);
@@ -190,7 +206,7 @@ fq_status jit_project_bits(int32_t col_dtype, const ProjLaunch &P, uint64_t *d_b
 constexpr int select_threads() { return 256; }
 constexpr int select_rows_per_thread() { return 32; }
 constexpr int select_sleep() { return 2; }
-constexpr int64_t select_tile_rows() { return (int64_t)select_threads() * select_rows_per_thread(); }
+constexpr int64_t select_tile_rows(int n_cols = 1) { return (int64_t)select_threads() * project_cols_rows(n_cols); }
 fq_status jit_project_select(int32_t col_dtype, const ProjLaunch &P, const uint64_t *d_bitmap, uint64_t *status,
                              uint32_t *ticket, uint32_t *d_flags, uint64_t *d_total);
 // stream of DataBlocks of block_rows rows (fq_filter_project_blocks): block b's

@@ -45,7 +45,7 @@ FUNCTION_SYMBOLS = [
     "fq_function_display", "fq_function_set_depth", "fq_function_return_type", "fq_function_nullable",
     "fq_function_eval", "fq_function_accumulate", "fq_function_accumulate_result", "fq_function_merge_state",
     "fq_function_merge_result", "fq_data_value_arithmetic_op", "fq_data_value_aggregate_op",
-    "fq_functions_accumulate",
+    "fq_functions_accumulate", "fq_functions_eval",
 ]
 
 _protos = {
@@ -62,6 +62,8 @@ _protos = {
                                      P(C.c_int32), P(C.c_int64), P(C.c_int32), P(fq_scalar)]),
     "fq_function_accumulate": (C.c_int32, [OPT, OPT, P(fq_block)]),
     "fq_functions_accumulate": (C.c_int32, [OPT, P(OPT), C.c_int32, P(fq_block)]),
+    "fq_functions_eval": (C.c_int32, [OPT, P(OPT), C.c_int32, P(fq_block), P(C.c_void_p), C.c_size_t, C.c_void_p,
+                                      P(C.c_int32), P(C.c_int64), P(C.c_size_t), P(C.c_int32)]),
     "fq_function_accumulate_result": (C.c_int32, [OPT, P(fq_scalar), C.c_size_t, P(C.c_size_t)]),
     "fq_function_merge_state": (C.c_int32, [OPT, P(fq_scalar), C.c_size_t]),
     "fq_function_merge_result": (C.c_int32, [OPT, P(fq_scalar)]),
@@ -255,6 +257,44 @@ class Function:
         _sync_torch()
         arr = (OPT * max(1, len(funcs)))(*[f.h for f in funcs])
         check(lib.fq_functions_accumulate(engine.h, arr, len(funcs), C.byref(block._abi())))
+
+    @staticmethod
+    def eval_all(engine, funcs, block, blocks=False, cap=None):
+        """transform_projection.rs:45-56 for one block -- every function's
+        eval(...).to_array(rows) -- through fq_functions_eval, honouring the
+        block's filter.  -> (columns, fused), or with blocks=True (block-stream
+        geometry: block b's rows at b * block_rows of every column)
+        (columns, counts, fused); fused: one fused kernel served the call.
+        cap: bytes per output buffer (default: every row of the block)."""
+        import numpy as np
+        import torch
+
+        from . import ops
+
+        _sync_torch()
+        n, rows = len(funcs), block.num_rows()
+        if cap is None:
+            cap = max(8, rows * 8)
+        outs = [torch.empty(max(cap, 8), dtype=torch.uint8, device="cuda") for _ in funcs]
+        ptrs = (C.c_void_p * max(1, n))(*[o.data_ptr() for o in outs])
+        arr = (OPT * max(1, n))(*[f.h for f in funcs])
+        nb = -(-rows // block.block_rows) if blocks and block.block_rows > 0 else 0
+        counts = torch.zeros(max(nb, 1), dtype=torch.int64, device="cuda") if blocks else None
+        dts = (C.c_int32 * max(1, n))()
+        ln, nbytes, fused = C.c_int64(0), C.c_size_t(0), C.c_int32(0)
+        st = lib.fq_functions_eval(engine.h, arr, n, C.byref(block._abi()), ptrs, cap,
+                                   C.c_void_p(counts.data_ptr()) if blocks else None, dts, C.byref(ln),
+                                   C.byref(nbytes), C.byref(fused))
+        if st != abi.FQ_OK:
+            from ._lib import last_error
+
+            err = FQError(st, last_error())
+            err.needed = nbytes.value  # FQ_E_INVALID for a short cap: the bytes an output needs
+            raise err
+        cols = [ops.DeviceColumn(o, rows if blocks else ln.value, dts[j]) for j, o in enumerate(outs)]
+        if blocks:
+            return cols, counts[:nb].cpu().numpy().astype(np.int64), bool(fused.value)
+        return cols, bool(fused.value)
 
     def accumulate_result(self):
         n = C.c_size_t(0)

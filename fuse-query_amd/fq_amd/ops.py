@@ -362,6 +362,93 @@ def predicate_bitmap(col, pred, stream=None):
     return out
 
 
+def _project_exprs(values, dtype0):
+    """[fq_expr or None] -> the fq_expr array (None: column 0 itself)."""
+    exprs = (abi.fq_expr * max(len(values), 1))()
+    for j, v in enumerate(values):
+        if v is None:
+            v = abi.fq_expr()
+            v.n_steps = 0
+            v.out_dtype = dtype0
+        exprs[j] = v
+    return exprs
+
+
+def filter_project_columns(cols, pred, values, stream=None):
+    """fq_filter_project_columns over a list of DeviceColumns of one block
+    (expr.chain_columns / predicate_columns number them by position): the kept
+    rows (pred None = all) through each fq_expr of `values` (None = column 0
+    itself) -> [DeviceColumn] in row order."""
+    require_gpu()
+    n_out, n = len(values), cols[0].len
+    exprs = _project_exprs(values, cols[0].dtype)
+    outs = [empty_column(n, exprs[j].out_dtype) for j in range(n_out)]
+    ptrs = (C.c_void_p * max(n_out, 1))(*[o.ptr for o in outs])
+    ws = Workspace(lib.fq_filter_project_columns_workspace_bytes(n, len(cols)))
+    kept = C.c_int64(0)
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    check(lib.fq_filter_project_columns(arr, len(cols), C.byref(pred) if pred is not None else None, exprs, n_out,
+                                        ptrs, C.byref(kept), ws.ptr, ws.nbytes, _stream(stream)))
+    for o in outs:
+        o.len = kept.value
+    return outs
+
+
+def filter_project_blocks_columns(cols, block_rows, pred, values, stream=None, out_offset=0, fill=None):
+    """fq_filter_project_blocks_columns: filter_project_blocks over a list of
+    DeviceColumns of one block -> ([DeviceColumn of len rows per output],
+    per-block kept counts).  out_offset as filter_project_blocks; fill: a
+    uint64 the output buffers are set to first (tests: rows past a block's
+    count must be left as they were)."""
+    require_gpu()
+    n_out, n = len(values), cols[0].len
+    exprs = _project_exprs(values, cols[0].dtype)
+    outs = []
+    for j in range(n_out):
+        full = empty_column(n + out_offset, exprs[j].out_dtype)
+        if fill is not None:
+            full.buf.view(torch.int64).fill_(int(np.uint64(fill).astype(np.int64)))
+        outs.append(DeviceColumn(full.buf, n, exprs[j].out_dtype, offset=8 * out_offset) if out_offset else full)
+    ptrs = (C.c_void_p * max(n_out, 1))(*[o.ptr for o in outs])
+    nb = (1 if block_rows >= n else -(-n // block_rows)) if block_rows > 0 and n > 0 else 0
+    counts = Workspace(max(8 * nb, 8))
+    ws = Workspace(lib.fq_filter_project_blocks_workspace_bytes())
+    kept = C.c_int64(0)
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    check(lib.fq_filter_project_blocks_columns(arr, len(cols), block_rows, C.byref(pred) if pred is not None else None,
+                                               exprs, n_out, ptrs, counts.ptr, C.byref(kept), ws.ptr, ws.nbytes,
+                                               _stream(stream)))
+    cnt = counts.buf[:8 * nb].view(torch.int64).cpu().numpy() if nb else np.zeros(0, np.int64)
+    return outs, cnt, kept.value
+
+
+def predicate_bitmap_columns(cols, pred, stream=None):
+    """fq_predicate_bitmap_columns: the predicate over a list of DeviceColumns
+    as a Boolean column."""
+    require_gpu()
+    out = empty_column(cols[0].len, abi.DT_BOOLEAN)
+    flag = Workspace(4)
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    check(lib.fq_predicate_bitmap_columns(arr, len(cols), C.byref(pred), C.c_void_p(out.ptr), flag.ptr,
+                                          _stream(stream)))
+    return out
+
+
+def jit_prepare_project_columns(dtypes, pred=None, values=(None,), block_rows=0, length=1 << 30, lengths=None):
+    """Compile the fused projection module of fq_filter_project_columns /
+    _blocks_columns / fq_predicate_bitmap_columns for this shape ahead of time
+    (works without a GPU: the source is then only compiled for gfx950).  One
+    dtype per column; returns True if the shape has a module."""
+    lens = list(lengths) if lengths is not None else [int(length)] * len(dtypes)
+    arr = (abi.fq_col * max(len(dtypes), 1))(*[abi.fq_col(None, int(n), dt, 0) for dt, n in zip(dtypes, lens)])
+    exprs = _project_exprs(values, dtypes[0] if dtypes else 0)
+    out = C.c_int32(0)
+    check(lib.fq_jit_prepare_project_columns(arr, len(dtypes), int(block_rows),
+                                             C.byref(pred) if pred is not None else None, exprs, len(values),
+                                             C.byref(out)))
+    return bool(out.value)
+
+
 def project_compile_check(col_dtype, pred=None, values=(None,)):
     """Generate + compile the fused projection module for this shape without
     running it (no GPU needed: gfx950 code object only).  Returns the

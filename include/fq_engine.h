@@ -317,6 +317,34 @@ fq_status fq_function_accumulate(fq_engine *e, fq_function *f, const fq_block *b
  * first failing function's error is returned (the reference's `?`); the
  * functions before it have accumulated.  Complete when the call returns.   */
 fq_status fq_functions_accumulate(fq_engine *e, fq_function *const *fs, int32_t n, const fq_block *b);
+/* ProjectionTransform's loop body for one block
+ * (transform_projection.rs:45-56: `for func in funcs {
+ * func.eval(&block)?.to_array(block.num_rows()) }`) over n handles at once,
+ * honouring the block's pending `filter` and its `block_rows`.  d_out: n
+ * caller-owned device buffers of `cap` bytes each.  out_dtypes[i]: the dtype
+ * of output i; *out_len: the rows every output holds; *out_bytes: the bytes an
+ * output needs (FQ_E_INVALID when cap is short).
+ *   d_counts == NULL  each output holds the kept rows concatenated, as n
+ *                     fq_function_eval calls would leave them;
+ *   d_counts != NULL  block-stream geometry (fq_filter_project_blocks): block
+ *                     b's rows at [b * block_rows, + d_counts[b]) of each
+ *                     output (device int64 per block), *out_len the rows kept
+ *                     over all blocks; needs block_rows >=
+ *                     FQ_PROJECT_MIN_BLOCK_ROWS and cap >= 8 x the block's
+ *                     rows (FQ_E_INVALID), 64-bit outputs only.
+ * When the filter and every function are expressions over up to
+ * FQ_MAX_SCAN_COLS 64-bit columns (at most FQ_MAX_PROJECT functions, the JIT
+ * on), ONE fused kernel serves the whole call -- no compacted copy of the
+ * block, no array per expression node -- and *fused = 1; the contiguous form
+ * writes straight into d_out when cap >= 8 x the block's rows.  Otherwise
+ * *fused = 0: either the functions fuse but the filter does not (or its
+ * columns would not fit beside theirs) -- its Boolean column is then evaluated
+ * first, node by node, and the fused kernel reads it -- or the block is
+ * materialised once and each function evaluated.  Results and errors are
+ * those of n fq_function_eval calls.  Complete when the call returns.      */
+fq_status fq_functions_eval(fq_engine *e, fq_function *const *fs, int32_t n, const fq_block *b, void *const *d_out,
+                            size_t cap, int64_t *d_counts, int32_t *out_dtypes, int64_t *out_len, size_t *out_bytes,
+                            int32_t *fused);
 /* states: the function's partial state vector (aggregates in depth order);
  * *n = its length (FQ_E_INVALID when cap is short, *n = the size needed)   */
 fq_status fq_function_accumulate_result(const fq_function *f, fq_scalar *states, size_t cap, size_t *n);

@@ -359,6 +359,46 @@ fq_status fq_blocks_compact(int32_t n_cols, const void *const *d_in, int64_t len
 fq_status fq_predicate_bitmap(const fq_col *col, const fq_pred *pred, uint64_t *d_bitmap, uint32_t *d_flag,
                               void *stream);
 
+/* ---- Filter -> Projection over up to FQ_MAX_SCAN_COLS 64-bit columns of one block ----
+ * (`SELECT a * b, a + c WHERE c < k`: FilterTransform's and
+ * ProjectionTransform's expression_executor range over every field of a
+ * DataBlock, function_field.rs:33-40, transform_filter.rs:38-55,
+ * transform_projection.rs:45-56).  The columns and every column reference
+ * follow fq_aggregate_columns (the encoding documented there): equal len,
+ * UINT64 / INT64 / FLOAT64 each (FQ_E_UNSUPPORTED for a narrow one,
+ * FQ_E_INVALID for unequal lengths or n_cols outside 1..FQ_MAX_SCAN_COLS); the
+ * predicate and each values[j] may start from, and read, different columns
+ * (values[j].n_steps == 0: column 0 itself).  Outputs, predicate kinds, the
+ * error order, statuses and texts are the single-column entry points'; with
+ * n_cols == 1 each call IS its single-column entry point.  More than one
+ * column runs on hipRTC-specialised kernels only (FQ_E_UNSUPPORTED with
+ * FQ_JIT_OFF or without hipRTC).
+ *
+ * fq_filter_project_columns: the contiguous (look-back) kernel; its tile, and
+ * so the workspace's status words, depend on n_cols.
+ * fq_filter_project_blocks_columns: the block-stream kernel, with
+ * fq_filter_project_blocks' geometry, block_rows >= FQ_PROJECT_MIN_BLOCK_ROWS
+ * rule and workspace (fq_filter_project_blocks_workspace_bytes).
+ * fq_predicate_bitmap_columns: the predicate alone as a Boolean column.      */
+size_t fq_filter_project_columns_workspace_bytes(int64_t len, int32_t n_cols);
+fq_status fq_filter_project_columns(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *values,
+                                    int32_t n_out, void *const *d_out, int64_t *out_len, void *d_ws, size_t ws_bytes,
+                                    void *stream);
+fq_status fq_filter_project_blocks_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                           const fq_expr *values, int32_t n_out, void *const *d_out,
+                                           int64_t *d_counts, int64_t *out_len, void *d_ws, size_t ws_bytes,
+                                           void *stream);
+fq_status fq_predicate_bitmap_columns(const fq_col *cols, int32_t n_cols, const fq_pred *pred, uint64_t *d_bitmap,
+                                      uint32_t *d_flag, void *stream);
+/* Compiles (and caches) the module those three calls use for this shape (one
+ * module holds all their kernels; block_rows is 0 or a block-stream block size,
+ * checked only).  The columns' data may be NULL.  *specialised = 1 when the
+ * shape has a module (0 with FQ_JIT_OFF or without hipRTC: the caller's unfused
+ * path answers).  Without a GPU the generated source is compiled for gfx950
+ * only to validate it.                                                        */
+fq_status fq_jit_prepare_project_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                         const fq_expr *values, int32_t n_out, int32_t *specialised);
+
 /* ---- AggregateFinal state merge (host, function_aggregator.rs:106-139) ----
  * Merges `n` partial states in the given order into *out (wrapping sum,
  * summed counts/blocks, max, min, OR-ed flags).  All dtypes must match.      */

@@ -9,6 +9,7 @@ checked against numpy on a prefix.  Prints one JSON document.
 
 usage: python tools/bench_kernels.py [--rows 1.25e9] [--reps 10] > gpurun_out/kernels.json
        python tools/bench_kernels.py --only q6 [--q6-rows 134217728] [--reps 20]   (the q6 lines alone)
+       python tools/bench_kernels.py --only pcols [--q6-rows 134217728] [--reps 20]   (Filter -> Projection over 3 columns)
 """
 import argparse
 import ctypes as C
@@ -160,18 +161,118 @@ def q6_lines(n, reps, st, res):
                                           "bytes_ratio": moved / (24 * n)}})
 
 
+def pcols_lines(n, reps, st, res):
+    """SELECT a*b, a+c WHERE c < 3<<61 over 3 u64 splitmix columns: ONE fq_filter_project_blocks_columns /
+    fq_filter_project_columns launch (24 B read + 16 B written per kept row), beside -- in the same process -- the
+    unfused path for the same statement (what ProjectionTransform runs when the shape does not fuse:
+    fq_compare, fq_filter_compact of every column, fq_arith per expression node on the kept rows) and the
+    single-column p1 shape through fq_filter_project_blocks.  Every launch event-timed; the entry points
+    synchronise their stream for the kept-row count, so each sample holds that host sync too."""
+    from fq_amd.expr import Col, chain_columns, load, predicate_columns
+    U = abi.DT_UINT64
+    k38 = 3 << 61
+    c, a, b = (ops.splitmix_column(seed, 0, n) for seed in (101, 102, 103))
+    dts = [U, U, U]
+    pred = predicate_columns(dts, [], "<", k38)
+    vals = (abi.fq_expr * 2)(chain_columns(dts, [load(1), ("*", Col(2))])[0], chain_columns(dts, [load(1), ("+", Col(0))])[0])
+    cols = (abi.fq_col * 3)(c.col(), a.col(), b.col())
+    o0, o1 = ops.empty_column(n, U), ops.empty_column(n, U)
+    outs = (C.c_void_p * 2)(o0.ptr, o1.ptr)
+    B = 10000
+    nb = -(-n // B)
+    counts = ops.Workspace(8 * nb)
+    bws = ops.Workspace(lib.fq_filter_project_blocks_workspace_bytes())
+    cws = ops.Workspace(lib.fq_filter_project_columns_workspace_bytes(n, 3))
+    kept = C.c_int64(0)
+
+    def rec(name, ts, nbytes, note=""):
+        ms = statistics.median(ts)
+        gbps = nbytes / (ms * 1e-3) / 1e9
+        res.append({"kernel": name, "ms": ms, "ms_min": min(ts), "ms_max": max(ts), "reps": len(ts),
+                    "algorithmic_bytes": nbytes, "achieved_gbps": gbps, "frac_of_peak": gbps / PEAK,
+                    "frac_of_peak_min_max": [nbytes / (max(ts) * 1e-3) / 1e9 / PEAK, nbytes / (min(ts) * 1e-3) / 1e9 / PEAK],
+                    "note": note})
+        print("%-58s %8.3f ms [%.3f .. %.3f]  %7.0f GB/s  %4.1f %%" % (name, ms, min(ts), max(ts), gbps,
+                                                                     100 * gbps / PEAK), file=sys.stderr)
+        return ms
+
+    def blocks():
+        check(lib.fq_filter_project_blocks_columns(cols, 3, B, C.byref(pred), vals, 2, outs, counts.ptr, C.byref(kept),
+                                                   bws.ptr, bws.nbytes, st))
+
+    def contiguous():
+        check(lib.fq_filter_project_columns(cols, 3, C.byref(pred), vals, 2, outs, C.byref(kept), cws.ptr, cws.nbytes, st))
+
+    hc, ha, hb = (x.to_numpy() for x in (c, a, b))
+    keep = hc < np.uint64(k38)
+    m = int(keep.sum())
+    with np.errstate(over="ignore"):
+        w0, w1 = ha[keep] * hb[keep], ha[keep] + hc[keep]
+    ts = timed_all(blocks, reps)
+    assert kept.value == m
+    cnt = counts.buf[:8 * nb].view(torch.int64).cpu().numpy()
+    k0 = int(cnt[0])
+    assert k0 == int(keep[:B].sum()) and np.array_equal(o0.to_numpy()[:k0], w0[:k0]) and np.array_equal(o1.to_numpy()[:k0], w1[:k0])
+    f_blk = rec("pcols a*b, a+c where c<k, 3 u64 columns, 10,000-row blocks", ts, 24 * n + 16 * m,
+                "fq_filter_project_blocks_columns")
+    ts = timed_all(contiguous, reps)
+    assert kept.value == m and np.array_equal(o0.to_numpy()[:m], w0) and np.array_equal(o1.to_numpy()[:m], w1)
+    f_con = rec("pcols a*b, a+c where c<k, 3 u64 columns, contiguous", ts, 24 * n + 16 * m, "fq_filter_project_columns")
+
+    # the unfused path for the same statement (this tree with the JIT off, the parent commit's only path)
+    bm = ops.empty_column(n, abi.DT_BOOLEAN)
+    kc, ka, kb = (ops.empty_column(n, U) for _ in range(3))
+    fws = ops.Workspace(lib.fq_filter_workspace_bytes(n))
+    bound = abi.fq_value(U, 1, k38)
+    cc = c.col()
+
+    def unfused():
+        check(lib.fq_compare(abi.CMP_BY_SYM["<"], C.byref(cc), None, None, C.byref(bound), C.c_void_p(bm.ptr), n, None, st))
+        for src, out in ((c, kc), (a, ka), (b, kb)):
+            sc = src.col()
+            check(lib.fq_filter_compact(C.byref(sc), C.c_void_p(bm.ptr), C.c_void_p(out.ptr), C.byref(kept), fws.ptr,
+                                        fws.nbytes, st))
+        k = kept.value
+        for op, l, r, o in (("*", ka, kb, o0), ("+", ka, kc, o1)):
+            lc, rc, oc = (abi.fq_col(C.c_void_p(x.ptr), k, U, 0) for x in (l, r, o))
+            check(lib.fq_arith(abi.OP_BY_SYM[op], C.byref(lc), None, C.byref(rc), None, C.byref(oc), None, st))
+
+    ts = timed_all(unfused, reps)
+    assert kept.value == m and np.array_equal(o0.to_numpy()[:m], w0) and np.array_equal(o1.to_numpy()[:m], w1)
+    moved = (8 * n + n // 8) + 3 * (8 * n + n // 8 + 8 * m) + 2 * 24 * m
+    u = rec("pcols unfused: compare, 3 compactions, 2 arith", ts, moved,
+            "six launches; includes fq_filter_compact's host syncs; bytes = what the path moves")
+
+    # the single-column p1 shape: number+1, number/2 where number%8<3 (bench.py --query p1)
+    p1 = predicate(U, [("%", 8)], "<", 3)
+    v1 = (abi.fq_expr * 2)(chain(U, [("+", 1)])[0], chain(U, [("/", 2)])[0])
+    ac = a.col()
+
+    def single():
+        check(lib.fq_filter_project_blocks(C.byref(ac), B, C.byref(p1), v1, 2, outs, counts.ptr, C.byref(kept), bws.ptr,
+                                           bws.nbytes, st))
+
+    ts = timed_all(single, reps)
+    m1 = kept.value
+    assert m1 == int((ha % np.uint64(8) < np.uint64(3)).sum())
+    rec("single column p1: x+1, x/2 where x%8<3, 10,000-row blocks", ts, 8 * n + 16 * m1, "fq_filter_project_blocks, same process")
+    res.append({"pcols_unfused_over_fused": {"block_stream": u / f_blk, "contiguous": u / f_con,
+                                             "bytes_ratio": moved / (24 * n + 16 * m)},
+                "gate_fused_below_unfused": bool(f_blk < u and f_con < u)})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=float, default=1.25e9)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--only", choices=["q6"], default=None, help="run only the named group of lines")
+    ap.add_argument("--only", choices=["q6", "pcols"], default=None, help="run only the named group of lines")
     ap.add_argument("--q6-rows", type=float, default=float(1 << 27))
     args = ap.parse_args()
     n = int(args.rows)
     st = ops._stream()
     res = []
-    if args.only == "q6":
-        q6_lines(int(args.q6_rows), args.reps, st, res)
+    if args.only in ("q6", "pcols"):
+        (q6_lines if args.only == "q6" else pcols_lines)(int(args.q6_rows), args.reps, st, res)
         print(json.dumps({"rows": int(args.q6_rows), "peak_gbps": PEAK, "device": torch.cuda.get_device_name(0),
                           "kernels": res}, indent=1))
         return

@@ -173,14 +173,16 @@ bool FieldFunction::to_chain(const DataSchema &s, FusedChain &c, FusedColumns *c
     c = FusedChain{};
     if (cols) {
         // one column may be narrow (the interpreting scan reads it); with a
-        // second one in the list every column is 64-bit
+        // second one in the list every column is 64-bit, unless the list is
+        // typed (fq_aggregate_typed reads any numeric column)
         const int k = cols->index(name_, dt);
         if (k < 0) return false;
-        if (cols->names.size() > 1)
+        if (cols->names.size() > 1 && !cols->typed)
             for (DataType d : cols->dtypes)
                 if (!is_chain_dtype(d)) return false;
         c.start = k;
     }
+    c.typed = cols && cols->typed;
     c.column = name_;
     c.col_dtype = dt;
     c.expr.n_steps = 0;
@@ -244,13 +246,13 @@ static bool tree_fusion_enabled() {
 static bool push_step(FusedChain &c, int32_t op, bool column_operand, const DataValue *k, bool reversed,
                       const FusedChain *col = nullptr) {
     if (c.expr.n_steps >= FQ_MAX_STEPS) return false;
-    if (!is_chain_dtype(c.col_dtype)) return false;
-    if (col && !is_chain_dtype(col->col_dtype)) return false;
+    if (!c.typed && !is_chain_dtype(c.col_dtype)) return false;
+    if (!c.typed && col && !is_chain_dtype(col->col_dtype)) return false;
     const DataType odt = column_operand ? (col ? col->col_dtype : c.col_dtype) : k->dtype;
     int32_t ct = 0;
     const int32_t l = reversed ? odt : c.out_dtype, r = reversed ? c.out_dtype : odt;
     if (fqc::numerical_coercion(fqc::arith_op_str(op), l, r, &ct) != FQ_OK) return false;
-    if (!is_chain_dtype(ct)) return false;
+    if (!c.typed && !is_chain_dtype(ct)) return false;
     fq_step &st = c.expr.steps[c.expr.n_steps];
     st.op = op;
     st.operand = column_operand ? FQ_OPERAND_COLUMN : FQ_OPERAND_CONST;
@@ -262,6 +264,20 @@ static bool push_step(FusedChain &c, int32_t op, bool column_operand, const Data
     c.expr.out_dtype = ct;
     c.out_dtype = ct;
     return true;
+}
+
+// a step or comparison type that is not 64-bit: the shape is fq_aggregate_typed's
+static bool expr_is_narrow(const fq_expr &e) {
+    for (int i = 0; i < e.n_steps; ++i)
+        if (e.steps[i].op != FQ_OP_PUSH && e.steps[i].op != FQ_OP_LOAD && !is_chain_dtype(e.steps[i].dtype)) return true;
+    return false;
+}
+static bool pred_is_narrow(const FusedPred &p) {
+    if (p.pred.kind == FQ_PRED_EXPR) return !is_chain_dtype(p.pred.cmp_dtype) || expr_is_narrow(p.pred.lhs);
+    if (p.pred.kind == FQ_PRED_TREE)
+        for (int i = 0; i < p.tree.n_leaves; ++i)
+            if (!is_chain_dtype(p.tree.leaves[i].cmp_dtype) || expr_is_narrow(p.tree.leaves[i].lhs)) return true;
+    return false;
 }
 
 static bool numeric_constant(const Function &f, const DataValue *&v) {
@@ -299,9 +315,11 @@ bool ArithmeticFunction::to_chain(const DataSchema &s, FusedChain &c, FusedColum
     if (!lok || !rok || (l.column != r.column && !cols) || !tree_fusion_enabled()) return false;
     if (l.expr.n_steps + r.expr.n_steps + 2 > FQ_MAX_STEPS) return false;
     const int depth = std::max(l.depth, 1 + r.depth);
-    if (depth > FQ_MAX_STACK || !is_chain_dtype(l.col_dtype) || !is_chain_dtype(r.col_dtype)) return false;
+    if (depth > FQ_MAX_STACK) return false;
+    if (!l.typed && (!is_chain_dtype(l.col_dtype) || !is_chain_dtype(r.col_dtype))) return false;
     int32_t ct = 0;
-    if (fqc::numerical_coercion(fqc::arith_op_str(op_), l.out_dtype, r.out_dtype, &ct) != FQ_OK || !is_chain_dtype(ct))
+    if (fqc::numerical_coercion(fqc::arith_op_str(op_), l.out_dtype, r.out_dtype, &ct) != FQ_OK ||
+        (!l.typed && !is_chain_dtype(ct)))
         return false;
     c = l;
     fq_step &push = c.expr.steps[c.expr.n_steps++];
@@ -361,12 +379,12 @@ static int32_t flip(int32_t cmp) {
 // A column right-hand side is `col` (an identity chain); null: lhs's own column.
 static bool make_pred(const FusedChain &lhs, int32_t cmp, bool column_rhs, const DataValue *k, FusedPred &p,
                       const FusedChain *col = nullptr) {
-    if (!is_chain_dtype(lhs.col_dtype)) return false;
-    if (col && !is_chain_dtype(col->col_dtype)) return false;
+    if (!lhs.typed && !is_chain_dtype(lhs.col_dtype)) return false;
+    if (!lhs.typed && col && !is_chain_dtype(col->col_dtype)) return false;
     const DataType rdt = column_rhs ? (col ? col->col_dtype : lhs.col_dtype) : k->dtype;
     int32_t ct = 0;
     if (fqc::equal_coercion(fqc::cmp_op_str(cmp), lhs.out_dtype, rdt, &ct) != FQ_OK) return false;
-    if (!is_chain_dtype(ct)) return false;
+    if (!lhs.typed && !is_chain_dtype(ct)) return false;
     p = FusedPred{};
     p.column = lhs.column;
     p.col_dtype = lhs.col_dtype;
@@ -1207,11 +1225,29 @@ void AggFusion::add(AggregatorFunction *agg, const DataBlock &b) {
     // hipRTC kernels and the FQ_OP_LOAD step to fit; a shape that does not fit
     // (a fifth column, a ninth step, a deeper stack, the JIT off) takes the
     // unfused branch below like any other unfusable shape.
+    // With the JIT on the columns, steps and comparisons may have any numeric
+    // type: a shape with a narrow one among them is one fq_aggregate_typed scan
+    // over device columns (a lone narrow column with neither expression nor
+    // fused predicate keeps the precompiled identity scan).
     FusedColumns cols;
+    cols.typed = tree_fusion_enabled();
     bool ok = !b.filter || b.filter->to_pred(s, fp, &cols);
     if (ok) ok = agg->arg().to_chain(s, fc, &cols);
     fq_expr value_expr = fc.expr;
-    if (ok && cols.names.size() > 1) {
+    bool typed = false;
+    if (ok && cols.typed) {
+        for (DataType d : cols.dtypes) typed = typed || !is_chain_dtype(d);
+        typed = typed || expr_is_narrow(fc.expr) || (b.filter && pred_is_narrow(fp));
+        if (cols.names.size() == 1 && fc.expr.n_steps == 0 && !b.filter) typed = false;
+    }
+    if (ok && typed) {
+        // (a cast per change of acc's type may leave the lowered program no room: unfused then)
+        ok = fc.with_load(value_expr) &&
+             fqk::typed_scan_fits(cols.dtypes.data(), (int32_t)cols.names.size(), b.filter ? fp.get() : nullptr,
+                                  value_expr.n_steps ? &value_expr : nullptr);
+        for (const std::string &name : cols.names) ok = ok && b.column_by_name(name).on_device();
+        fc.columns = fp.columns = cols.names;
+    } else if (ok && cols.names.size() > 1) {
         ok = tree_fusion_enabled() && fc.with_load(value_expr);
         for (DataType d : cols.dtypes) ok = ok && is_chain_dtype(d);
         fc.columns = fp.columns = cols.names;
@@ -1237,7 +1273,8 @@ void AggFusion::add(AggregatorFunction *agg, const DataBlock &b) {
         g = &cur_.back();
         g->key = key;
         g->col = b.column_by_name(cols.names[0]);
-        if (cols.names.size() > 1)
+        g->typed = typed;
+        if (cols.names.size() > 1 || typed)
             for (const std::string &name : cols.names) g->cols.push_back(b.column_by_name(name));
         g->value = fc;
         g->value_expr = value_expr;
@@ -1275,8 +1312,9 @@ void AggFusion::end_block() {
             e1 = ctx_.res->take_event();
         }
         if (prof && n_cols) {
-            check_fq(fq_jit_prepare_columns(cs, n_cols, g.block_rows, g.has_pred ? g.pred.get() : nullptr,
-                                            g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask, nullptr));
+            check_fq((g.typed ? fq_jit_prepare_typed : fq_jit_prepare_columns)(
+                cs, n_cols, g.block_rows, g.has_pred ? g.pred.get() : nullptr,
+                g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask, nullptr));
         } else if (prof && (g.has_pred || g.value.expr.n_steps)) {
             // compile a specialised scan (first use of this expression shape)
             // outside the timed region (identity scans are precompiled)
@@ -1295,9 +1333,9 @@ void AggFusion::end_block() {
             if (ticket_ && ticket_->group()) ticket_->group()->before_launch(ctx_);
             if (pairs) check_hip(hipEventRecord(e0, stream_), "hipEventRecord");
             if (n_cols)
-                check_fq(fq_aggregate_columns(cs, n_cols, g.block_rows, pred,
-                                              g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask,
-                                              (fq_agg_state *)dst, res_->ws, res_->ws_bytes, stream_));
+                check_fq((g.typed ? fq_aggregate_typed : fq_aggregate_columns)(
+                    cs, n_cols, g.block_rows, pred, g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask,
+                    (fq_agg_state *)dst, res_->ws, res_->ws_bytes, stream_));
             else
                 check_fq(fq_aggregate(&c, g.block_rows, pred, val, g.mask, (fq_agg_state *)dst, res_->ws,
                                       res_->ws_bytes, stream_));
@@ -1309,9 +1347,10 @@ void AggFusion::end_block() {
         if (pairs) events_.push_back({e0, e1});
         ctx_.rt->stats.scan_launches++;
         ctx_.rt->stats.scan_rows += (uint64_t)g.col.len;
-        // every column of the scan is read once: 8 x columns x rows over several
-        ctx_.rt->stats.scan_bytes +=
-            (uint64_t)g.col.len * (uint64_t)dtype_size(g.col.dtype) * (uint64_t)(n_cols ? n_cols : 1);
+        // every column of the scan is read once: the sum of the widths x rows
+        uint64_t row_bytes = n_cols ? 0 : (uint64_t)dtype_size(g.col.dtype);
+        for (const Column &gc : g.cols) row_bytes += (uint64_t)dtype_size(gc.dtype);
+        ctx_.rt->stats.scan_bytes += (uint64_t)g.col.len * row_bytes;
         // a stream-ordered column (hipFreeAsync on the queue the scan was just
         // enqueued on) may be dropped now: its memory returns to the pool only
         // after the scan -- so a query over generated chunks holds one chunk per

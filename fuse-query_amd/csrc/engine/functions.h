@@ -21,6 +21,9 @@ namespace fq {
 struct FusedColumns {
     std::vector<std::string> names;
     std::vector<DataType> dtypes;
+    // columns, steps and comparisons of any numeric type (fq_aggregate_typed:
+    // AggFusion sets it while the JIT is on); else narrow types do not fuse
+    bool typed = false;
     // the column's number (a new one if it has none yet); -1: no room left
     int index(const std::string &name, DataType dt);
 };
@@ -36,6 +39,7 @@ struct FusedChain {
     DataType out_dtype = FQ_DT_NULL;
     int depth = 0;  // value-stack depth the expression tree needs (FQ_OP_PUSH)
     int start = 0;  // the number of `column` in the list
+    bool typed = false;  // lowered under a FusedColumns list with `typed` set
     std::vector<std::string> columns;  // the scan's column list (AggFusion fills it in)
     std::string key() const;
     // the expression as fq_aggregate_columns takes it: FQ_OP_LOAD in front when
@@ -453,6 +457,7 @@ class AggFusion {
         std::string key;
         Column col;
         std::vector<Column> cols;  // more than one column: fq_aggregate_columns
+        bool typed = false;        // a narrow column, step or comparison: fq_aggregate_typed over cols (one or more)
         fq_expr value_expr{};      // value.expr, FQ_OP_LOAD in front when it starts from another column than 0
         FusedChain value;
         bool has_pred = false;

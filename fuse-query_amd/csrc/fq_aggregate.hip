@@ -389,10 +389,32 @@ static bool is_chain_dtype(int32_t dt) {
     return dt == FQ_DT_UINT64 || dt == FQ_DT_INT64 || dt == FQ_DT_FLOAT64;
 }
 
-static fq_status push_cast(int32_t from, int32_t to, KProg &out) {
+// position in numerical_coercion's order (fq_common.cpp order[]): the coerced
+// type of two is the one that comes first; -1 for a non-numeric type
+static int coercion_rank(int32_t dt) {
+    static const int32_t order[] = {FQ_DT_FLOAT64, FQ_DT_FLOAT32, FQ_DT_INT64,  FQ_DT_INT32, FQ_DT_INT16,
+                                    FQ_DT_INT8,    FQ_DT_UINT64,  FQ_DT_UINT32, FQ_DT_UINT16, FQ_DT_UINT8};
+    for (int i = 0; i < 10; ++i)
+        if (order[i] == dt) return i;
+    return -1;
+}
+static int32_t coerced(int32_t l, int32_t r) { return coercion_rank(l) <= coercion_rank(r) ? l : r; }
+
+static fq_status push_cast(int32_t from, int32_t to, KProg &out, bool typed = false) {
     if (from == to) return FQ_OK;
     if (out.n >= (int)(sizeof(out.s) / sizeof(out.s[0])))
         return fqc::fail(FQ_E_UNSUPPORTED, "expression too long for the fused device path");
+    if (typed) {  // one of the 45 casts towards an earlier type of the order
+        if (coercion_rank(to) < 0 || coercion_rank(from) < coercion_rank(to))
+            return fqc::fail(FQ_E_INVALID, std::string("fq_step: numerical_coercion never casts ") +
+                                               fqc::dtype_name(from) + " to " + fqc::dtype_name(to));
+        KStep &s = out.s[out.n++];
+        s = KStep{};
+        s.code = K_CAST;
+        s.sdtype = from;
+        s.dtype = to;
+        return FQ_OK;
+    }
     KStep &s = out.s[out.n++];
     s = KStep{};
     s.dtype = to;
@@ -408,7 +430,10 @@ static fq_status push_cast(int32_t from, int32_t to, KProg &out) {
 // fq_expr (semantic) -> KProg (lowered).  Returns the resulting dtype.
 // n_cols == 0: the single-column entry points, which ignore the column indices
 // (every reference is the one column, of dtype cdt[0]).
-static fq_status lower_expr_impl(const fq_expr &e, const int32_t *cdt, int n_cols, KProg &out, int32_t &res_dtype) {
+// typed: fq_aggregate_typed -- any numeric column and step type; every step's
+// type must be what numerical_coercion yields for acc and the operand.
+static fq_status lower_expr_impl(const fq_expr &e, const int32_t *cdt, int n_cols, KProg &out, int32_t &res_dtype,
+                                 bool typed = false) {
     out.n = 0;
     const int32_t col_dtype = cdt[0];
     // the column a step's `bits` names (-1: out of range)
@@ -416,7 +441,7 @@ static fq_status lower_expr_impl(const fq_expr &e, const int32_t *cdt, int n_col
     int32_t acc = col_dtype;
     if (e.n_steps < 0 || e.n_steps > FQ_MAX_STEPS)
         return fqc::fail(FQ_E_INVALID, "fq_expr: n_steps out of range");
-    if (e.n_steps > 0 && !is_chain_dtype(col_dtype))
+    if (e.n_steps > 0 && !typed && !is_chain_dtype(col_dtype))
         return fqc::fail(FQ_E_UNSUPPORTED, std::string("fused expressions over ") + fqc::dtype_name(col_dtype) +
                                                " columns are not supported on the device path");
     int32_t stack[FQ_MAX_STACK];
@@ -437,7 +462,8 @@ static fq_status lower_expr_impl(const fq_expr &e, const int32_t *cdt, int n_col
         }
         if (st.op == FQ_OP_PUSH) {  // expression tree: acc onto the stack, restart from the column
             if (depth >= FQ_MAX_STACK) return fqc::fail(FQ_E_UNSUPPORTED, "expression tree too deep for the fused device path");
-            if (!is_chain_dtype(col_dtype)) return fqc::fail(FQ_E_UNSUPPORTED, "fused expression trees need a 64-bit column");
+            if (!typed && !is_chain_dtype(col_dtype))
+                return fqc::fail(FQ_E_UNSUPPORTED, "fused expression trees need a 64-bit column");
             if (out.n >= (int)(sizeof(out.s) / sizeof(out.s[0])))
                 return fqc::fail(FQ_E_UNSUPPORTED, "expression too long for the fused device path");
             const int c = col_of(st.bits);
@@ -451,23 +477,46 @@ static fq_status lower_expr_impl(const fq_expr &e, const int32_t *cdt, int n_col
             acc = cdt[c];
             continue;
         }
-        if (!is_chain_dtype(st.dtype))
-            return fqc::fail(FQ_E_UNSUPPORTED, "fused step dtype must be UInt64, Int64 or Float64");
+        if (typed ? !fqc::dtype_is_numeric(st.dtype) : !is_chain_dtype(st.dtype))
+            return fqc::fail(FQ_E_UNSUPPORTED, typed ? "fused step dtype must be numeric"
+                                                     : "fused step dtype must be UInt64, Int64 or Float64");
+        // typed: the step's type against numerical_coercion(acc, operand)
+        auto coercion_ok = [&](int32_t odt, const char *what) -> fq_status {
+            if (coerced(acc, odt) == st.dtype) return FQ_OK;
+            return fqc::fail(FQ_E_INVALID, std::string("fq_step: ") + fqc::dtype_name(odt) + " " + what + " in a " +
+                                               fqc::dtype_name(st.dtype) + " step over " + fqc::dtype_name(acc) +
+                                               " (numerical_coercion gives " + fqc::dtype_name(coerced(acc, odt)) + ")");
+        };
         int32_t sdt = 0;
         if (st.operand == FQ_OPERAND_STACK) {
             if (depth == 0) return fqc::fail(FQ_E_INVALID, "fq_step: stack operand without a pushed value");
             sdt = stack[--depth];
-            if (sdt != st.dtype && !(sdt == FQ_DT_UINT64 && st.dtype != FQ_DT_UINT64) &&
+            if (typed) {
+                fq_status cs = coercion_ok(sdt, "stack operand");
+                if (cs != FQ_OK) return cs;
+            } else if (sdt != st.dtype && !(sdt == FQ_DT_UINT64 && st.dtype != FQ_DT_UINT64) &&
                 !(sdt == FQ_DT_INT64 && st.dtype == FQ_DT_FLOAT64))
                 return fqc::fail(FQ_E_UNSUPPORTED, std::string("fused cast ") + fqc::dtype_name(sdt) + " -> " +
                                                        fqc::dtype_name(st.dtype) + " is not supported on the device path");
         } else if (st.operand != FQ_OPERAND_CONST && st.operand != FQ_OPERAND_COLUMN) {
             return fqc::fail(FQ_E_INVALID, "fq_step: bad operand kind");
         }
-        fq_status s = push_cast(acc, st.dtype, out);
-        if (s != FQ_OK) return s;
         int ocol = 0;
-        if (st.operand == FQ_OPERAND_COLUMN) {
+        if (typed) {
+            if (st.operand == FQ_OPERAND_COLUMN) {
+                ocol = col_of(st.bits);
+                if (ocol < 0) return fqc::fail(FQ_E_INVALID, "fq_step: column index out of range");
+                fq_status cs = coercion_ok(cdt[ocol], "column operand");
+                if (cs != FQ_OK) return cs;
+            } else if (st.operand == FQ_OPERAND_CONST && coercion_rank(st.dtype) > coercion_rank(acc)) {
+                return fqc::fail(FQ_E_INVALID, std::string("fq_step: a ") + fqc::dtype_name(st.dtype) +
+                                                   " step over " + fqc::dtype_name(acc) +
+                                                   " (numerical_coercion never yields it)");
+            }
+        }
+        fq_status s = push_cast(acc, st.dtype, out, typed);
+        if (s != FQ_OK) return s;
+        if (!typed && st.operand == FQ_OPERAND_COLUMN) {
             ocol = col_of(st.bits);
             if (ocol < 0) return fqc::fail(FQ_E_INVALID, "fq_step: column index out of range");
             if (cdt[ocol] == FQ_DT_FLOAT64 && st.dtype != FQ_DT_FLOAT64)
@@ -485,8 +534,9 @@ static fq_status lower_expr_impl(const fq_expr &e, const int32_t *cdt, int n_col
         k.sdtype = sdt;
         k.col = ocol;
         k.c = st.bits;
-        const bool konst = st.operand == FQ_OPERAND_CONST && !st.reversed;
-        if (st.dtype == FQ_DT_FLOAT64) {
+        // typed scans keep the constant a kernel argument of a plain '/' or '%'
+        const bool konst = st.operand == FQ_OPERAND_CONST && !st.reversed && !typed;
+        if (fqc::dtype_is_float(st.dtype)) {
             switch (st.op) {
                 case FQ_OP_ADD: k.code = K_ADD_F; break;
                 case FQ_OP_SUB: k.code = K_SUB_F; break;
@@ -496,7 +546,7 @@ static fq_status lower_expr_impl(const fq_expr &e, const int32_t *cdt, int n_col
                 default: return fqc::fail(FQ_E_INVALID, "fq_step: bad op");
             }
         } else {
-            const bool u = st.dtype == FQ_DT_UINT64;
+            const bool u = fqc::dtype_is_unsigned_int(st.dtype);
             switch (st.op) {
                 case FQ_OP_ADD: k.code = K_ADD_I; break;
                 case FQ_OP_SUB: k.code = K_SUB_I; break;
@@ -559,20 +609,34 @@ fq_status lower_expr_cols(const fq_expr &e, const int32_t *cdt, int n_cols, KPro
     return lower_expr_impl(e, cdt, n_cols, out, res_dtype);
 }
 
+fq_status lower_expr_typed(const fq_expr &e, const int32_t *cdt, int n_cols, KProg &out, int32_t &res_dtype) {
+    return lower_expr_impl(e, cdt, n_cols, out, res_dtype, true);
+}
+
 // fq_pred (semantic) -> KPred (lowered): predicate program cast to the
 // comparison type.
 static fq_status lower_pred_impl(const fq_pred *pred, const int32_t *cdt, int n_cols, int64_t len, bool need_data,
-                                 KPred &out) {
+                                 KPred &out, bool typed = false) {
     out = KPred{};
     out.kind = pred ? pred->kind : FQ_PRED_NONE;
     const int32_t col_dtype = cdt[0];
     // the right-hand column of a comparison in cmp_dtype: its index in *rc
-    auto rhs_col = [cdt, n_cols](int32_t rhs_operand, uint64_t bits, int32_t cmp_dtype, int32_t *rc) -> fq_status {
+    // (typed: cmp_dtype against equal_coercion of the left side's type ldt and the right side)
+    auto rhs_col = [cdt, n_cols, typed](int32_t rhs_operand, uint64_t bits, int32_t cmp_dtype, int32_t *rc,
+                                        int32_t ldt) -> fq_status {
         *rc = 0;
+        if (typed && rhs_operand != FQ_OPERAND_COLUMN && rhs_operand != FQ_OPERAND_CONST)
+            return fqc::fail(FQ_E_INVALID, "fq_pred: bad rhs_operand");
         if (rhs_operand != FQ_OPERAND_COLUMN) return FQ_OK;
         if (n_cols > 0) {
             if (bits >= (uint64_t)n_cols) return fqc::fail(FQ_E_INVALID, "fq_pred: column index out of range");
             *rc = (int32_t)bits;
+        }
+        if (typed) {
+            if (coerced(ldt, cdt[*rc]) == cmp_dtype) return FQ_OK;
+            return fqc::fail(FQ_E_INVALID, std::string("fq_pred: ") + fqc::dtype_name(ldt) + " compared with a " +
+                                               fqc::dtype_name(cdt[*rc]) + " column as " + fqc::dtype_name(cmp_dtype) +
+                                               " (equal_coercion gives " + fqc::dtype_name(coerced(ldt, cdt[*rc])) + ")");
         }
         if (cdt[*rc] == FQ_DT_FLOAT64 && cmp_dtype != FQ_DT_FLOAT64)
             return fqc::fail(FQ_E_INVALID, "fq_pred: Float64 column compared as integer");
@@ -582,13 +646,18 @@ static fq_status lower_pred_impl(const fq_pred *pred, const int32_t *cdt, int n_
     };
     if (out.kind == FQ_PRED_EXPR) {
         int32_t ldt = col_dtype;
-        fq_status s = lower_expr_impl(pred->lhs, cdt, n_cols, out.lhs, ldt);
+        fq_status s = lower_expr_impl(pred->lhs, cdt, n_cols, out.lhs, ldt, typed);
         if (s != FQ_OK) return s;
-        if (!is_chain_dtype(pred->cmp_dtype))
-            return fqc::fail(FQ_E_UNSUPPORTED, "fused comparison type must be UInt64, Int64 or Float64");
-        s = push_cast(ldt, pred->cmp_dtype, out.lhs);
+        if (typed ? !fqc::dtype_is_numeric(pred->cmp_dtype) : !is_chain_dtype(pred->cmp_dtype))
+            return fqc::fail(FQ_E_UNSUPPORTED, typed ? "fused comparison type must be numeric"
+                                                     : "fused comparison type must be UInt64, Int64 or Float64");
+        if (typed && (pred->cmp < FQ_CMP_EQ || pred->cmp > FQ_CMP_GTEQ)) return fqc::fail(FQ_E_INVALID, "fq_pred: bad cmp");
+        // (typed: the right side first -- its message names the types that do not coerce)
+        if (typed) s = rhs_col(pred->rhs_operand, pred->rhs_bits, pred->cmp_dtype, &out.rhs_col, ldt);
         if (s != FQ_OK) return s;
-        s = rhs_col(pred->rhs_operand, pred->rhs_bits, pred->cmp_dtype, &out.rhs_col);
+        s = push_cast(ldt, pred->cmp_dtype, out.lhs, typed);
+        if (s != FQ_OK) return s;
+        if (!typed) s = rhs_col(pred->rhs_operand, pred->rhs_bits, pred->cmp_dtype, &out.rhs_col, ldt);
         if (s != FQ_OK) return s;
         out.cmp = pred->cmp;
         out.cmp_dtype = pred->cmp_dtype;
@@ -603,7 +672,7 @@ static fq_status lower_pred_impl(const fq_pred *pred, const int32_t *cdt, int n_
         if (t->n_leaves < 1 || t->n_leaves > FQ_MAX_PRED_LEAVES || t->n_prog < 1 ||
             t->n_prog > 2 * FQ_MAX_PRED_LEAVES)
             return fqc::fail(FQ_E_INVALID, "fq_pred_tree: leaf / program count out of range");
-        if (fqc::dtype_size(col_dtype) != 8)
+        if (!typed && fqc::dtype_size(col_dtype) != 8)
             return fqc::fail(FQ_E_UNSUPPORTED, "fused predicates need a 64-bit column");
         out.n_leaves = t->n_leaves;
         out.n_prog = t->n_prog;
@@ -611,14 +680,17 @@ static fq_status lower_pred_impl(const fq_pred *pred, const int32_t *cdt, int n_
             const fq_pred_leaf &lf = t->leaves[i];
             KLeaf &k = out.leaves[i];
             int32_t ldt = col_dtype;
-            fq_status s = lower_expr_impl(lf.lhs, cdt, n_cols, k.lhs, ldt);
+            fq_status s = lower_expr_impl(lf.lhs, cdt, n_cols, k.lhs, ldt, typed);
             if (s != FQ_OK) return s;
-            if (!is_chain_dtype(lf.cmp_dtype))
-                return fqc::fail(FQ_E_UNSUPPORTED, "fused comparison type must be UInt64, Int64 or Float64");
-            s = push_cast(ldt, lf.cmp_dtype, k.lhs);
+            if (typed ? !fqc::dtype_is_numeric(lf.cmp_dtype) : !is_chain_dtype(lf.cmp_dtype))
+                return fqc::fail(FQ_E_UNSUPPORTED, typed ? "fused comparison type must be numeric"
+                                                         : "fused comparison type must be UInt64, Int64 or Float64");
+            if (typed) s = rhs_col(lf.rhs_operand, lf.rhs_bits, lf.cmp_dtype, &k.rhs_col, ldt);
+            if (s != FQ_OK) return s;
+            s = push_cast(ldt, lf.cmp_dtype, k.lhs, typed);
             if (s != FQ_OK) return s;
             if (lf.cmp < FQ_CMP_EQ || lf.cmp > FQ_CMP_GTEQ) return fqc::fail(FQ_E_INVALID, "fq_pred_leaf: bad cmp");
-            s = rhs_col(lf.rhs_operand, lf.rhs_bits, lf.cmp_dtype, &k.rhs_col);
+            if (!typed) s = rhs_col(lf.rhs_operand, lf.rhs_bits, lf.cmp_dtype, &k.rhs_col, ldt);
             if (s != FQ_OK) return s;
             k.cmp = lf.cmp;
             k.cmp_dtype = lf.cmp_dtype;
@@ -660,6 +732,11 @@ fq_status lower_pred(const fq_pred *pred, int32_t col_dtype, int64_t len, bool n
 fq_status lower_pred_cols(const fq_pred *pred, const int32_t *cdt, int n_cols, int64_t len, bool need_data,
                           KPred &out) {
     return lower_pred_impl(pred, cdt, n_cols, len, need_data, out);
+}
+
+fq_status lower_pred_typed(const fq_pred *pred, const int32_t *cdt, int n_cols, int64_t len, bool need_data,
+                           KPred &out) {
+    return lower_pred_impl(pred, cdt, n_cols, len, need_data, out, true);
 }
 
 template <typename TIn, typename V, int PRED, bool CHAIN>
@@ -1000,9 +1077,182 @@ static fq_status aggregate_cols(const fq_col *cols, int32_t n_cols, int64_t bloc
     return dispatch_finalize(L, blocks, empty_if_zero, d_out);
 }
 
+// ---------------------------------------------------------------------------
+// fq_aggregate_typed: columns, steps and comparisons of any numeric type
+// ---------------------------------------------------------------------------
+static const char *kTypedNeedsJit =
+    "scans over narrow or mixed-width columns run on the hipRTC kernels only (FQ_JIT is off or hipRTC is "
+    "unavailable)";
+
+static fq_status check_cols_typed(const fq_col *cols, int32_t n_cols, bool need_data, const char *who) {
+    const std::string W = std::string(who) + ": ";
+    if (!cols) return fqc::fail(FQ_E_INVALID, W + "NULL argument");
+    if (n_cols < 1 || n_cols > FQ_MAX_SCAN_COLS)
+        return fqc::fail(FQ_E_INVALID, W + "n_cols must be 1.." + std::to_string(FQ_MAX_SCAN_COLS) +
+                                           ", got " + std::to_string(n_cols));
+    for (int j = 0; j < n_cols; ++j) {
+        if (cols[j].len < 0) return fqc::fail(FQ_E_INVALID, W + "negative length");
+        if (cols[j].len != cols[0].len)
+            return fqc::fail(FQ_E_INVALID, W + "column " + std::to_string(j) + " has " +
+                                               std::to_string(cols[j].len) + " rows, column 0 has " +
+                                               std::to_string(cols[0].len));
+        if (!fqc::dtype_is_numeric(cols[j].dtype))
+            return fqc::internal(std::string("Unsupported data_array_aggregate for data type: ") +
+                                 fqc::dtype_name(cols[j].dtype));
+        if (need_data && cols[j].len > 0 && !cols[j].data)
+            return fqc::fail(FQ_E_INVALID, W + "NULL column data");
+        if (((uintptr_t)cols[j].data) % fqc::dtype_size(cols[j].dtype))
+            return fqc::fail(FQ_E_INVALID, W + "column not aligned to its element size");
+    }
+    return FQ_OK;
+}
+
+// every column, step and comparison type 64-bit: the call is fq_aggregate_columns
+static bool expr_is_64(const fq_expr *e) {
+    if (!e) return true;
+    for (int i = 0; i < e->n_steps && i < FQ_MAX_STEPS; ++i)
+        if (e->steps[i].op != FQ_OP_PUSH && e->steps[i].op != FQ_OP_LOAD && !is_chain_dtype(e->steps[i].dtype))
+            return false;
+    return true;
+}
+static bool call_is_64(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *value) {
+    for (int j = 0; j < n_cols; ++j)
+        if (!is_chain_dtype(cols[j].dtype)) return false;
+    if (!expr_is_64(value)) return false;
+    if (pred && pred->kind == FQ_PRED_EXPR) return is_chain_dtype(pred->cmp_dtype) && expr_is_64(&pred->lhs);
+    if (pred && pred->kind == FQ_PRED_TREE && pred->tree)
+        for (int l = 0; l < pred->tree->n_leaves && l < FQ_MAX_PRED_LEAVES; ++l)
+            if (!is_chain_dtype(pred->tree->leaves[l].cmp_dtype) || !expr_is_64(&pred->tree->leaves[l].lhs))
+                return false;
+    return true;
+}
+
+static fq_status plan_scan_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                 const fq_expr *value, uint32_t agg_mask, bool need_data, Launch &L, bool &chain,
+                                 uint64_t &blocks, int &empty_if_zero) {
+    const int64_t len = cols[0].len;
+    if (block_rows <= 0) block_rows = len > 0 ? len : 1;
+    L = Launch{};
+    L.typed = true;
+    L.col = cols[0].data;
+    L.n = len;
+    L.block_rows = block_rows;
+    L.mask = agg_mask;
+    L.n_cols = n_cols;
+    for (int j = 0; j < n_cols; ++j) {
+        L.cols[j] = cols[j].data;
+        L.cdt[j] = cols[j].dtype;
+    }
+    chain = value && value->n_steps > 0;
+    int32_t vdt = L.cdt[0];
+    if (chain) {
+        fq_status s = lower_expr_typed(*value, L.cdt, n_cols, L.val, vdt);
+        if (s != FQ_OK) return s;
+    }
+    L.vdtype = vdt;
+    fq_status ps = lower_pred_typed(pred, L.cdt, n_cols, len, need_data, L.pred);
+    if (ps != FQ_OK) return ps;
+
+    blocks = len == 0 ? 0 : (uint64_t)((len + block_rows - 1) / block_rows);
+    L.block_mode = L.pred.kind != FQ_PRED_NONE && (agg_mask & FQ_AGG_SUM) && blocks > 1;
+    empty_if_zero = (L.pred.kind != FQ_PRED_NONE && blocks == 1) ? 1 : 0;
+
+    typed_group(L.cdt, n_cols, &L.group, &L.prefetch);
+    const int64_t G = L.group;
+    // the grouped loads need the same rows of every column at a multiple of G elements
+    bool same_phase = true, aligned = true;
+    const int64_t phase0 = (int64_t)((((uintptr_t)cols[0].data) / fqc::dtype_size(L.cdt[0])) % G);
+    for (int j = 0; j < n_cols; ++j) {
+        const int64_t ph = (int64_t)((((uintptr_t)cols[j].data) / fqc::dtype_size(L.cdt[j])) % G);
+        same_phase = same_phase && ph == phase0;
+        aligned = aligned && ph == 0;
+    }
+    const int cus = fqc::device_cu_count();
+    const int max_grid = cus * 8 < kMaxPartials ? cus * 8 : kMaxPartials;
+    if (L.block_mode) {
+        int64_t grid = ((int64_t)blocks + (kThreads / kWave) - 1) / (kThreads / kWave);
+        L.grid = (int)(grid < max_grid ? (grid < 1 ? 1 : grid) : max_grid);
+        L.head = 0;
+        L.vec = aligned && (block_rows % G) == 0;
+    } else {
+        L.vec = same_phase;
+        int64_t head = (G - phase0) % G;
+        if (head > len) head = len;
+        L.head = L.vec ? head : 0;
+        const int64_t tile_rows = (int64_t)kThreads * G;
+        int64_t grid = (len + tile_rows - 1) / tile_rows;
+        if (grid < 1) grid = 1;
+        const int64_t flat_max = (int64_t)cus * scan_wg_per_cu();
+        L.grid = (int)(grid < flat_max ? grid : flat_max);
+    }
+    return FQ_OK;
+}
+
+bool typed_scan_fits(const int32_t *cdt, int32_t n_cols, const fq_pred *pred, const fq_expr *value) {
+    if (!cdt || n_cols < 1 || n_cols > FQ_MAX_SCAN_COLS) return false;
+    KProg val;
+    KPred kp;
+    int32_t vdt = cdt[0];
+    if (value && value->n_steps > 0 && lower_expr_typed(*value, cdt, n_cols, val, vdt) != FQ_OK) return false;
+    return lower_pred_typed(pred, cdt, n_cols, 0, false, kp) == FQ_OK;
+}
+
 }  // namespace fqk
 
 extern "C" {
+
+fq_status fq_aggregate_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                             const fq_expr *value, uint32_t agg_mask, fq_agg_state *d_out, void *d_ws,
+                             size_t ws_bytes, void *stream) {
+    using namespace fqk;
+    fq_status s = check_cols_typed(cols, n_cols, true, "fq_aggregate_typed");
+    if (s != FQ_OK) return s;
+    if (call_is_64(cols, n_cols, pred, value))
+        return fq_aggregate_columns(cols, n_cols, block_rows, pred, value, agg_mask, d_out, d_ws, ws_bytes, stream);
+    if (!d_out || !d_ws) return fqc::fail(FQ_E_INVALID, "fq_aggregate_typed: NULL argument");
+    if (ws_bytes < kPartialsBytes) return fqc::fail(FQ_E_INVALID, "fq_aggregate_typed: workspace too small");
+    if (agg_mask & ~(uint32_t)(FQ_AGG_MIN | FQ_AGG_MAX | FQ_AGG_SUM | FQ_AGG_COUNT))
+        return fqc::fail(FQ_E_INVALID, "fq_aggregate_typed: unknown bits in agg_mask");
+    Launch L;
+    bool chain = false;
+    uint64_t blocks = 0;
+    int empty_if_zero = 0;
+    s = plan_scan_typed(cols, n_cols, block_rows, pred, value, agg_mask, true, L, chain, blocks, empty_if_zero);
+    if (s != FQ_OK) return s;
+    L.stream = (hipStream_t)stream;
+    L.parts = (Partial *)d_ws;
+    if (agg_mask == FQ_AGG_COUNT && !chain && L.pred.kind == FQ_PRED_NONE) {
+        L.grid = 0;  // count(column): rows, not values (see launch_finalize)
+        return dispatch_finalize(L, blocks, empty_if_zero, d_out);
+    }
+    bool jitted = false;
+    s = jit_scan(cols[0].dtype, chain, L, &jitted, true);
+    if (s != FQ_OK) return s;
+    if (!jitted) return fqc::fail(FQ_E_UNSUPPORTED, kTypedNeedsJit);
+    return dispatch_finalize(L, blocks, empty_if_zero, d_out);
+}
+
+fq_status fq_jit_prepare_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                               const fq_expr *value, uint32_t agg_mask, int32_t *specialised) {
+    using namespace fqk;
+    if (specialised) *specialised = 0;
+    fq_status s = check_cols_typed(cols, n_cols, false, "fq_jit_prepare_typed");
+    if (s != FQ_OK) return s;
+    if (call_is_64(cols, n_cols, pred, value))
+        return fq_jit_prepare_columns(cols, n_cols, block_rows, pred, value, agg_mask, specialised);
+    Launch L;
+    bool chain = false;
+    uint64_t blocks = 0;
+    int empty_if_zero = 0;
+    s = plan_scan_typed(cols, n_cols, block_rows, pred, value, agg_mask, false, L, chain, blocks, empty_if_zero);
+    if (s != FQ_OK) return s;
+    bool ok = false;
+    s = jit_prepare(cols[0].dtype, chain, L, &ok);
+    if (s != FQ_OK) return s;
+    if (!ok) return fqc::fail(FQ_E_UNSUPPORTED, kTypedNeedsJit);
+    if (specialised) *specialised = 1;
+    return FQ_OK;
+}
 
 fq_status fq_aggregate_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
                                const fq_expr *value, uint32_t agg_mask, fq_agg_state *d_out, void *d_ws,

@@ -247,10 +247,14 @@ bool cast_scalar(uint64_t bits, int32_t from, int32_t to, uint64_t *out) {
     }
     if (dtype_is_float(to)) {
         double d;
-        if (dtype_is_float(from)) __builtin_memcpy(&d, &bits, 8);
-        else if (dtype_is_signed_int(from)) d = (double)(int64_t)bits;
-        else d = (double)bits;
-        if (to == FQ_DT_FLOAT32) d = (double)(float)d;
+        if (dtype_is_float(from)) {
+            __builtin_memcpy(&d, &bits, 8);
+            if (to == FQ_DT_FLOAT32) d = (double)(float)d;
+        } else if (to == FQ_DT_FLOAT32) {  // one rounding, as arrow's cast: not through binary64
+            d = dtype_is_signed_int(from) ? (double)(float)(int64_t)bits : (double)(float)bits;
+        } else {
+            d = dtype_is_signed_int(from) ? (double)(int64_t)bits : (double)bits;
+        }
         __builtin_memcpy(out, &d, 8);
         return true;
     }

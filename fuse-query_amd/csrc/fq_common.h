@@ -78,4 +78,10 @@ fq_status filter_project_blocks_enqueue_columns(const fq_col *cols, int32_t n_co
                                                 uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
                                                 void *ev_end, void *stream);
 fq_status filter_project_blocks_result(const uint64_t *h_result, int64_t *out_len);
+// Whether fq_aggregate_typed's lowering takes this predicate and value over
+// columns of dtypes cdt (fq_aggregate.hip): a dry run that launches nothing.
+// Every change of acc's type costs a lowered step for its cast, so a chain of
+// FQ_MAX_STEPS steps over narrow types may not fit; the engine asks before it
+// commits a block to the typed scan (false: the unfused branch answers).
+bool typed_scan_fits(const int32_t *cdt, int32_t n_cols, const fq_pred *pred, const fq_expr *value);
 }  // namespace fqk

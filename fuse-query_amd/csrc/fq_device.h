@@ -46,6 +46,9 @@ enum Code : int32_t {
     K_DIVM32_U,  // u64 '/' by a constant d <= 65535: long division in 32/16/16-bit digits,
                  // each step a 32-bit magic divide (every partial dividend < d * 2^16)
     K_LOAD,      // scans over several columns: acc = column `col` (hipRTC kernels only)
+    K_CAST,      // typed scans: acc of type `sdtype` -> `dtype`, any of numerical_coercion's 45 casts
+                 // (an integer outside `dtype`'s range is arrow's null: FQ_STATE_CAST_NULL on a live
+                 // row; integer -> float rounds to nearest; Float32 -> Float64 is exact)
 };
 
 struct KStep {

@@ -953,6 +953,547 @@ __device__ __forceinline__ Partial wg_reduce(Acc acc) {
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// Typed scans (fq_aggregate_typed): columns, steps and comparisons of any of
+// the ten numeric types.  A source of its own -- shapes whose types are all
+// 64-bit never come here and keep the text above.  Every value of the
+// per-row programs is a C++ variable of its own type (a step of <= 32 bits is
+// 32-bit VALU work: a UInt8 column at HBM rate delivers eight times the rows
+// of a UInt64 one, so 64-bit work per row would become the bound); casts,
+// wrapping arithmetic and the range checks are the templates of kTypedCommon.
+// ---------------------------------------------------------------------------
+const char *tname(int32_t dt) {
+    switch (dt) {
+        case FQ_DT_INT8: return "i8";
+        case FQ_DT_INT16: return "i16";
+        case FQ_DT_INT32: return "i32";
+        case FQ_DT_INT64: return "i64";
+        case FQ_DT_UINT8: return "u8";
+        case FQ_DT_UINT16: return "u16";
+        case FQ_DT_UINT32: return "u32";
+        case FQ_DT_UINT64: return "u64";
+        case FQ_DT_FLOAT32: return "f32";
+        case FQ_DT_FLOAT64: return "f64";
+        default: return nullptr;
+    }
+}
+
+const char *kTypedCommon = R"(
+typedef unsigned long long u64;
+typedef long long i64;
+typedef unsigned int u32;
+typedef int i32;
+typedef unsigned short u16;
+typedef short i16;
+typedef unsigned char u8;
+typedef signed char i8;
+typedef float f32;
+typedef double f64;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+struct Partial { u64 sum, max, min, count, blocks; u32 flags; int dtype; };
+#define FQ_FLT(T) (__is_same(T, f32) || __is_same(T, f64))
+#define FQ_SGN(T) (T(-1) < T(0))
+template <int N> struct UW { typedef u32 t; };
+template <> struct UW<8> { typedef u64 t; };
+// an integer type's maximum
+template <typename T> __device__ constexpr u64 fq_hi() { return ~0ull >> (64 - 8 * (int)sizeof(T) + (FQ_SGN(T) ? 1 : 0)); }
+// arrow's cast: an integer outside T's range is null (FQ_STATE_CAST_NULL on a
+// live row); integer -> float rounds to nearest; f32 -> f64 is exact
+template <typename T, typename S> __device__ __forceinline__ T fq_cast(S v, u32 &flags, u32 live) {
+    if constexpr (FQ_FLT(T)) {
+        return (T)v;
+    } else {
+        bool bad;
+        if constexpr (FQ_SGN(S)) {
+            const i64 w = (i64)v;
+            if constexpr (FQ_SGN(T)) bad = w < -(i64)fq_hi<T>() - 1 || w > (i64)fq_hi<T>();
+            else bad = w < 0 || (u64)w > fq_hi<T>();
+        } else {
+            bad = (u64)v > fq_hi<T>();
+        }
+        flags |= (bad && live) ? 4u : 0u;  // FQ_STATE_CAST_NULL
+        return (T)v;
+    }
+}
+// a constant in the step's type (fq_value encoding)
+template <typename T> __device__ __forceinline__ T fq_const(u64 b) {
+    if constexpr (__is_same(T, f64)) return __builtin_bit_cast(f64, b);
+    else if constexpr (__is_same(T, f32)) return (f32)__builtin_bit_cast(f64, b);
+    else return (T)b;
+}
+template <typename T> __device__ __forceinline__ u64 fq_bits(T v) {
+    if constexpr (__is_same(T, f64)) return __builtin_bit_cast(u64, v);
+    else if constexpr (__is_same(T, f32)) return __builtin_bit_cast(u64, (f64)v);
+    else if constexpr (FQ_SGN(T)) return (u64)(i64)v;
+    else return (u64)v;
+}
+// integers wrap modulo 2^w; floats round once per step in their own format
+template <typename T> __device__ __forceinline__ T fq_add(T l, T r) {
+    if constexpr (FQ_FLT(T)) return l + r;
+    else return (T)((typename UW<sizeof(T)>::t)l + (typename UW<sizeof(T)>::t)r);
+}
+template <typename T> __device__ __forceinline__ T fq_sub(T l, T r) {
+    if constexpr (FQ_FLT(T)) return l - r;
+    else return (T)((typename UW<sizeof(T)>::t)l - (typename UW<sizeof(T)>::t)r);
+}
+template <typename T> __device__ __forceinline__ T fq_mul(T l, T r) {
+    if constexpr (FQ_FLT(T)) return l * r;
+    else return (T)((typename UW<sizeof(T)>::t)l * (typename UW<sizeof(T)>::t)r);
+}
+// '/' and '%' truncate; T::MIN / -1 wraps to T::MIN and T::MIN % -1 is 0
+template <typename T> __device__ __forceinline__ T fq_div(T l, T r, u32 &flags, u32 live) {
+    flags |= (r == T(0) && live) ? 2u : 0u;  // FQ_STATE_DIV_ZERO
+    if constexpr (FQ_FLT(T)) {
+        return l / r;
+    } else {
+        if (r == T(0)) return T(0);
+        if constexpr (FQ_SGN(T)) {
+            if (r == T(-1)) return (T)((typename UW<sizeof(T)>::t)0 - (typename UW<sizeof(T)>::t)l);
+        }
+        return (T)(l / r);
+    }
+}
+template <typename T> __device__ __forceinline__ T fq_mod(T l, T r, u32 &flags, u32 live) {
+    flags |= (r == T(0) && live) ? 2u : 0u;  // FQ_STATE_DIV_ZERO
+    if constexpr (__is_same(T, f32)) {
+        return fmodf(l, r);
+    } else if constexpr (__is_same(T, f64)) {
+        return fmod(l, r);
+    } else {
+        if (r == T(0)) return T(0);
+        if constexpr (FQ_SGN(T)) {
+            if (r == T(-1)) return T(0);
+        }
+        return (T)(l % r);
+    }
+}
+// max/min: a float NaN is ignored unless every folded value is NaN (the
+// running value starts at NaN); integers start at their limits
+template <typename T> __device__ __forceinline__ T vmax(T a, T b) {
+    if constexpr (FQ_FLT(T)) return (b > a || a != a) ? b : a;
+    else return b > a ? b : a;
+}
+template <typename T> __device__ __forceinline__ T vmin(T a, T b) {
+    if constexpr (FQ_FLT(T)) return (b < a || a != a) ? b : a;
+    else return b < a ? b : a;
+}
+template <typename T> __device__ __forceinline__ T fq_max_id() {
+    if constexpr (FQ_FLT(T)) return (T)__builtin_nan("");
+    else if constexpr (FQ_SGN(T)) return (T)(-(i64)fq_hi<T>() - 1);
+    else return T(0);
+}
+template <typename T> __device__ __forceinline__ T fq_min_id() {
+    if constexpr (FQ_FLT(T)) return (T)__builtin_nan("");
+    else return (T)fq_hi<T>();
+}
+template <typename T> __device__ __forceinline__ T shfl(T v, int m) {
+    if constexpr (sizeof(T) == 8) {
+        const u64 b = __builtin_bit_cast(u64, v);
+        const u32 lo = __shfl_xor((u32)(b & 0xffffffffu), m, 64);
+        const u32 hi = __shfl_xor((u32)(b >> 32), m, 64);
+        return __builtin_bit_cast(T, ((u64)hi << 32) | lo);
+    } else if constexpr (__is_same(T, f32)) {
+        return __shfl_xor(v, m, 64);
+    } else {
+        return (T)__shfl_xor((int)v, m, 64);
+    }
+}
+)";
+
+static_assert(FQ_STATE_CAST_NULL == 4u && FQ_STATE_DIV_ZERO == 2u, "the flag values written into kTypedCommon");
+
+struct TVal {
+    std::string e;  // a variable of the generated source
+    int32_t dt;
+};
+struct TGen {
+    int uid = 0;
+    int32_t cdt[FQ_MAX_SCAN_COLS] = {};
+    TVal X(int col) const { return TVal{"x" + std::to_string(col), cdt[col]}; }
+};
+
+std::string tcast(const TVal &v, int32_t to) {
+    if (v.dt == to) return v.e;
+    return std::string("fq_cast<") + tname(to) + ">(" + v.e + ", flags, live)";
+}
+
+// Straight-line code for one lowered program; `cur` is acc before and after.
+bool emit_prog_typed(TGen &g, std::string &body, const KProg &p, const std::string &prefix, TVal &cur) {
+    std::vector<TVal> stk;
+    for (int i = 0; i < p.n; ++i) {
+        const KStep &st = p.s[i];
+        const char *T = tname(st.dtype);
+        if (!T) return false;
+        const std::string t = "t" + std::to_string(g.uid++);
+        const std::string decl = std::string("    const ") + T + " " + t + " = ";
+        switch (st.code) {
+            case K_NOP: continue;
+            case K_CAST:
+                body += decl + tcast(cur, st.dtype) + ";\n";
+                cur = TVal{t, st.dtype};
+                continue;
+            case K_LOAD: cur = g.X(st.col); continue;
+            case K_PUSH:
+                stk.push_back(cur);
+                cur = g.X(st.col);
+                continue;
+            default: break;
+        }
+        std::string b;
+        if (st.operand == FQ_OPERAND_COLUMN) {
+            b = tcast(g.X(st.col), st.dtype);
+        } else if (st.operand == FQ_OPERAND_STACK) {
+            if (stk.empty()) return false;
+            b = tcast(stk.back(), st.dtype);
+            stk.pop_back();
+        } else {
+            b = std::string("fq_const<") + T + ">(c." + prefix + "[" + std::to_string(i) + "].c)";
+        }
+        const std::string a = tcast(cur, st.dtype);
+        const std::string LR = st.reversed ? b + ", " + a : a + ", " + b;
+        const char *fn = nullptr;
+        bool flagged = false;
+        switch (st.code) {
+            case K_ADD_I:
+            case K_ADD_F: fn = "fq_add"; break;
+            case K_SUB_I:
+            case K_SUB_F: fn = "fq_sub"; break;
+            case K_MUL_I:
+            case K_MUL_F: fn = "fq_mul"; break;
+            case K_DIV_U:
+            case K_DIV_S:
+            case K_DIV_F: fn = "fq_div", flagged = true; break;
+            case K_MOD_U:
+            case K_MOD_S:
+            case K_MOD_F: fn = "fq_mod", flagged = true; break;
+            default: return false;  // typed lowering emits no constant-divisor magic
+        }
+        body += decl + fn + "<" + T + ">(" + LR + (flagged ? ", flags, live" : "") + ");\n";
+        cur = TVal{t, st.dtype};
+    }
+    return stk.empty();
+}
+
+// `result = cmp(lhs(row), rhs)` in cmp_dtype
+bool emit_leaf_typed(TGen &g, int32_t cmp, int32_t cmp_dtype, int32_t rhs_operand, const KProg &lhs,
+                     const std::string &rhs, const std::string &prefix, int rhs_col, std::string &body,
+                     const std::string &result) {
+    const char *op = cmp_op(cmp);
+    const char *T = tname(cmp_dtype);
+    if (!op || !T) return false;
+    TVal cur = g.X(0);
+    if (!emit_prog_typed(g, body, lhs, prefix, cur)) return false;
+    const std::string r = rhs_operand == FQ_OPERAND_COLUMN ? tcast(g.X(rhs_col), cmp_dtype)
+                                                           : std::string("fq_const<") + T + ">(" + rhs + ")";
+    const std::string l = "l" + std::to_string(g.uid++), rr = "r" + std::to_string(g.uid++);
+    body += std::string("    const ") + T + " " + l + " = " + tcast(cur, cmp_dtype) + ";\n";
+    body += std::string("    const ") + T + " " + rr + " = " + r + ";\n";
+    body += "    " + result + " = " + l + " " + op + " " + rr + ";\n";
+    return true;
+}
+
+bool emit_pred_typed(TGen &g, const KPred &pr, std::string &body) {
+    if (pr.kind == FQ_PRED_TREE) {
+        for (int l = 0; l < pr.n_leaves; ++l) {
+            const std::string L = std::to_string(l);
+            body += "    bool b" + L + ";\n";
+            if (!emit_leaf_typed(g, pr.leaves[l].cmp, pr.leaves[l].cmp_dtype, pr.leaves[l].rhs_operand,
+                                 pr.leaves[l].lhs, "c.rl[" + L + "]", "pl[" + L + "]", pr.leaves[l].rhs_col, body,
+                                 "b" + L))
+                return false;
+        }
+        std::vector<std::string> st;
+        for (int i = 0; i < pr.n_prog; ++i) {
+            const int32_t t = pr.prog[i];
+            if (t >= 0 && t < pr.n_leaves) {
+                st.push_back("b" + std::to_string(t));
+            } else {
+                if (st.size() < 2) return false;
+                const std::string r = st.back();
+                st.pop_back();
+                const std::string l = st.back();
+                st.pop_back();
+                st.push_back("(" + l + (t == FQ_PRED_AND ? " & " : " | ") + r + ")");
+            }
+        }
+        if (st.size() != 1) return false;
+        body += "    return " + st[0] + ";\n";
+        return true;
+    }
+    body += "    bool b;\n";
+    if (!emit_leaf_typed(g, pr.cmp, pr.cmp_dtype, pr.rhs_operand, pr.lhs, "c.rhs", "p", pr.rhs_col, body, "b"))
+        return false;
+    body += "    return b;\n";
+    return true;
+}
+
+// The streaming loops of a typed scan: a lane owns G consecutive rows of a
+// tile of 256 * G rows and loads its G * w bytes of every column as one piece
+// (P@: a 1-, 2-, 4- or 8-byte word, or NP@ 16-byte vectors), so a wave's load
+// of a column is one contiguous run.  `head` < 0 (the columns share no phase,
+// or block mode off the group's grid): one row per lane per column.
+void gen_typed_loop(const Launch &L, std::string &src) {
+    const int K = L.n_cols;
+    auto FOR = [K](const std::string &t, const char *sep = "") {
+        std::string o;
+        for (int j = 0; j < K; ++j) {
+            std::string u = t;
+            for (size_t p = 0; (p = u.find('@', p)) != std::string::npos;) u.replace(p, 1, std::to_string(j));
+            o += (j ? sep : "") + u;
+        }
+        return o;
+    };
+    const std::string S8 = std::to_string(std::max(1, 8 / K));  // scalar loads per lane per column in flight
+    // LOAD(dst, pointer, group): the lane's pieces of every column
+    auto LOAD = [&FOR](const std::string &ind, const std::string &dst, const std::string &ptr, const std::string &gi) {
+        return FOR(ind + "_Pragma(\"unroll\") for (int q = 0; q < NP@; ++q) " + dst + "[q] = __builtin_nontemporal_load(" +
+                   ptr + "@ + (" + gi + ") * NP@ + q);\n");
+    };
+    // ROWS(raw, first row, live): the group's rows through fq_acc
+    auto ROWS = [&FOR](const std::string &ind, const std::string &raw, const std::string &i0, const std::string &live,
+                       const char *any) {
+        return FOR(ind + "TIn@ y@[G];\n" + ind + "__builtin_memcpy(&y@[0], &" + raw + "[0], G * sizeof(TIn@));\n") + ind +
+               "_Pragma(\"unroll\") for (int r = 0; r < G; ++r) " + any + "fq_acc(acc, " + FOR("y@[r]", ", ") + ", " + i0 +
+               " + r, " + live + ", c, bitmap);\n";
+    };
+    if (!L.block_mode) {
+        src += "\n    (void)R;\n"
+               "    const long long T = (long long)gridDim.x * 256;\n"
+               "    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;\n"
+               "    if (head >= 0) {\n"
+               "    const long long ngrp = (n - head) / G;\n";
+        src += FOR("    const P@ *__restrict__ pp@ = (const P@ *)(col@ + head);\n");
+        src += "    const long long ntiles = ngrp / 256;\n";
+        if (L.prefetch) {
+            src += "    // next tile's loads in flight while this tile is evaluated\n";
+            src += FOR("    P@ nxt@[NP@];\n");
+            src += "    if ((long long)blockIdx.x < ntiles) {\n" +
+                   LOAD("        ", "nxt@", "pp", "(long long)blockIdx.x * 256 + threadIdx.x") + "    }\n";
+            src += "    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {\n"
+                   "        const long long gi = t * 256 + threadIdx.x;\n";
+            src += FOR("        P@ raw@[NP@];\n        _Pragma(\"unroll\") for (int q = 0; q < NP@; ++q) raw@[q] = nxt@[q];\n");
+            src += "        const long long tn = t + gridDim.x;\n        if (tn < ntiles) {\n" +
+                   LOAD("            ", "nxt@", "pp", "tn * 256 + threadIdx.x") + "        }\n";
+        } else {
+            src += "    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {\n"
+                   "        const long long gi = t * 256 + threadIdx.x;\n";
+            src += FOR("        P@ raw@[NP@];\n") + LOAD("        ", "raw@", "pp", "gi");
+        }
+        src += ROWS("        ", "raw@", "head + gi * G", "1u", "") + "    }\n";
+        src += "    for (long long gi = ntiles * 256 + g; gi < ngrp; gi += T) {\n";
+        src += FOR("        P@ raw@[NP@];\n") + LOAD("        ", "raw@", "pp", "gi");
+        src += ROWS("        ", "raw@", "head + gi * G", "1u", "") + "    }\n";
+        src += "    const long long tail0 = head + ngrp * G;\n"
+               "    const long long nedge = head + (n - tail0);\n"
+               "    for (long long t = g; t < nedge; t += T) {\n"
+               "        const long long i = t < head ? t : tail0 + (t - head);\n"
+               "        fq_acc(acc, " + FOR("col@[i]", ", ") + ", i, 1u, c, bitmap);\n"
+               "    }\n"
+               "    } else {\n"
+               "    for (long long i = g; i < n; i += T * " + S8 + ") {\n";
+        src += FOR("        TIn@ y@[" + S8 + "];\n");
+        src += "#pragma unroll\n        for (int k = 0; k < " + S8 + "; ++k) {\n"
+               "            const long long ik = i + (long long)k * T;\n";
+        src += FOR("            y@[k] = ik < n ? __builtin_nontemporal_load(col@ + ik) : TIn@(0);\n");
+        src += "        }\n#pragma unroll\n        for (int k = 0; k < " + S8 + "; ++k) {\n"
+               "            const long long ik = i + (long long)k * T;\n"
+               "            fq_acc(acc, " + FOR("y@[k]", ", ") + ", ik, ik < n ? 1u : 0u, c, bitmap);\n"
+               "        }\n    }\n    }\n";
+        return;
+    }
+    // block mode: one wave per reference block, the per-block empty ballot
+    src += "\n    const int lane = threadIdx.x & 63;\n"
+           "    const long long w = ((long long)blockIdx.x * 256 + threadIdx.x) / 64;\n"
+           "    const long long W = ((long long)gridDim.x * 256) / 64;\n"
+           "    const long long nb = (n + R - 1) / R;\n"
+           "    const bool vec = head >= 0;\n"
+           "    for (long long b = w; b < nb; b += W) {\n"
+           "        const long long s = b * R;\n"
+           "        const long long e = (s + R < n) ? s + R : n;\n"
+           "        u32 any = 0;\n"
+           "        if (vec) {\n"
+           "            const long long ng = (e - s) / G;\n";
+    src += FOR("            const P@ *__restrict__ bp@ = (const P@ *)(col@ + s);\n");
+    src += "            for (long long v = lane; v < ng; v += 64 * BM_U) {\n";
+    src += FOR("                P@ raw@[BM_U][NP@];\n");
+    src += "#pragma unroll\n                for (int k = 0; k < BM_U; ++k) {\n"
+           "                    const long long vk = v + (long long)k * 64;\n"
+           "                    if (vk < ng) {\n" + LOAD("                        ", "raw@[k]", "bp", "vk") +
+           "                    } else {\n" +
+           FOR("                        _Pragma(\"unroll\") for (int q = 0; q < NP@; ++q) raw@[k][q] = P@{};\n") +
+           "                    }\n                }\n"
+           "#pragma unroll\n                for (int k = 0; k < BM_U; ++k) {\n"
+           "                    const long long vk = v + (long long)k * 64;\n"
+           "                    const u32 li = vk < ng ? 1u : 0u;\n" +
+           ROWS("                    ", "raw@[k]", "s + vk * G", "li", "any |= ") +
+           "                }\n            }\n"
+           "            for (long long i = s + ng * G + lane; i < e; i += 64)\n"
+           "                any |= fq_acc(acc, " + FOR("col@[i]", ", ") + ", i, 1u, c, bitmap);\n"
+           "            if (__ballot(any != 0) == 0ull) acc.flags |= " + std::to_string(FQ_STATE_ANY_EMPTY) + "u;\n"
+           "            continue;\n        }\n"
+           "        for (long long i = s + lane; i < e; i += 64 * " + S8 + ") {\n";
+    src += FOR("            TIn@ y@[" + S8 + "];\n");
+    src += "#pragma unroll\n            for (int k = 0; k < " + S8 + "; ++k) {\n"
+           "                const long long ik = i + (long long)k * 64;\n";
+    src += FOR("                y@[k] = ik < e ? __builtin_nontemporal_load(col@ + ik) : TIn@(0);\n");
+    src += "            }\n#pragma unroll\n            for (int k = 0; k < " + S8 + "; ++k) {\n"
+           "                const long long ik = i + (long long)k * 64;\n"
+           "                any |= fq_acc(acc, " + FOR("y@[k]", ", ") + ", ik, ik < e ? 1u : 0u, c, bitmap);\n"
+           "            }\n        }\n"
+           "        if (__ballot(any != 0) == 0ull) acc.flags |= " + std::to_string(FQ_STATE_ANY_EMPTY) + "u;\n"
+           "    }\n";
+}
+
+// Full kernel source of a typed shape.
+bool gen_typed_source(const Launch &L, bool chain, std::string &src) {
+    const int K = L.n_cols;
+    const char *V = tname(L.vdtype);
+    if (K < 1 || K > FQ_MAX_SCAN_COLS || !V || L.group < 1) return false;
+    TGen g;
+    std::string XP, XA;
+    int sum = 0;
+    for (int j = 0; j < K; ++j) {
+        if (!tname(L.cdt[j])) return false;
+        g.cdt[j] = L.cdt[j];
+        sum += fqc::dtype_size(L.cdt[j]);
+        const std::string J = std::to_string(j);
+        XP += (j ? ", TIn" : "TIn") + J + " x" + J;
+        XA += (j ? ", x" : "x") + J;
+    }
+    const int32_t pk = L.pred.kind;
+    const bool expr_pred = pk == FQ_PRED_EXPR || pk == FQ_PRED_TREE;
+    std::string pred_body, val_body;
+    if (expr_pred && !emit_pred_typed(g, L.pred, pred_body)) return false;
+    if (chain) {
+        TVal cur = g.X(0);
+        if (!emit_prog_typed(g, val_body, L.val, "v", cur)) return false;
+        val_body += "    return " + tcast(cur, L.vdtype) + ";\n";
+    } else {
+        val_body = "    return " + tcast(g.X(0), L.vdtype) + ";\n";
+    }
+
+    src = kTypedCommon;
+    src += "#define G " + std::to_string(L.group) + "\n";
+    for (int j = 0; j < K; ++j) {
+        const std::string J = std::to_string(j);
+        const int B = L.group * fqc::dtype_size(L.cdt[j]);  // bytes of a lane's piece
+        src += "typedef " + std::string(tname(L.cdt[j])) + " TIn" + J + ";\n";
+        src += "typedef " + std::string(B >= 16 ? "u32x4" : B == 8 ? "u64" : B == 4 ? "u32" : B == 2 ? "u16" : "u8") + " P" + J +
+               ";\n#define NP" + J + " " + std::to_string(B >= 16 ? B / 16 : 1) + "\n";
+    }
+    src += "typedef " + std::string(V) + " V;\n";
+    src += "struct Step { u64 c, m, s; };\nstruct Consts { u64 rhs; Step p[" + std::to_string(kSteps) +
+           "], v[" + std::to_string(kSteps) + "]; u64 rl[" + std::to_string(FQ_MAX_PRED_LEAVES) + "]; Step pl[" +
+           std::to_string(FQ_MAX_PRED_LEAVES) + "][" + std::to_string(kSteps) + "]; };\n";
+    src += "__device__ __forceinline__ bool fq_pred(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n";
+    src += expr_pred ? pred_body : "    return true;\n";
+    src += "}\n";
+    src += "__device__ __forceinline__ V fq_val(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n" + val_body + "}\n";
+    const uint32_t m = L.mask;
+    // block mode: the pieces of BM_U groups in flight, about 128 bytes per lane
+    src += "#define BM_U " + std::to_string(std::max(1, 128 / (L.group * sum))) + "\n";
+    src += "struct Acc { V sum, mx, mn; u64 cnt; u32 flags; };\n";
+    src += "__device__ __forceinline__ u32 fq_acc(Acc &acc, " + XP + ", long long idx, u32 live, const Consts &c,\n"
+           "                                      const u64 *__restrict__ bitmap) {\n"
+           "    u32 pass = live;\n";
+    if (expr_pred) src += "    pass &= fq_pred(" + XA + ", c, acc.flags, live) ? 1u : 0u;\n";
+    else if (pk == FQ_PRED_BITMAP)
+        src += "    if (live) pass &= (u32)((bitmap[idx >> 6] >> (idx & 63)) & 1ull);\n";
+    src += "    (void)idx; (void)bitmap;\n    const V v = fq_val(" + XA + ", c, acc.flags, pass);\n";
+    if (m & FQ_AGG_SUM) src += "    acc.sum = fq_add<V>(acc.sum, pass ? v : V(0));\n";
+    if (m & FQ_AGG_MAX) src += "    acc.mx = pass ? vmax(acc.mx, v) : acc.mx;\n";
+    if (m & FQ_AGG_MIN) src += "    acc.mn = pass ? vmin(acc.mn, v) : acc.mn;\n";
+    src += "    acc.cnt += pass;\n    return pass;\n}\n";
+    src += R"(
+__device__ __forceinline__ Partial wg_reduce(Acc acc) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        acc.sum = fq_add<V>(acc.sum, shfl(acc.sum, off));
+        acc.mx = vmax(acc.mx, shfl(acc.mx, off));
+        acc.mn = vmin(acc.mn, shfl(acc.mn, off));
+        acc.cnt += shfl(acc.cnt, off);
+        acc.flags |= (u32)__shfl_xor((int)acc.flags, off, 64);
+    }
+    __shared__ V s_sum[4], s_mx[4], s_mn[4];
+    __shared__ u64 s_cnt[4];
+    __shared__ u32 s_flags[4];
+    const int wave = threadIdx.x / 64;
+    if ((threadIdx.x & 63) == 0) {
+        s_sum[wave] = acc.sum; s_mx[wave] = acc.mx; s_mn[wave] = acc.mn;
+        s_cnt[wave] = acc.cnt; s_flags[wave] = acc.flags;
+    }
+    __syncthreads();
+    Partial p;
+    if (threadIdx.x == 0) {
+        V sum = s_sum[0], mx = s_mx[0], mn = s_mn[0];
+        u64 cnt = s_cnt[0];
+        u32 flags = s_flags[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            sum = fq_add<V>(sum, s_sum[w]); mx = vmax(mx, s_mx[w]); mn = vmin(mn, s_mn[w]);
+            cnt += s_cnt[w]; flags |= s_flags[w];
+        }
+        p.sum = fq_bits<V>(sum); p.max = fq_bits<V>(mx); p.min = fq_bits<V>(mn);
+        p.count = cnt; p.blocks = 0; p.flags = flags; p.dtype = )" + std::to_string(L.vdtype) + R"(;
+    }
+    return p;
+}
+)";
+    std::string cols_params;
+    for (int j = 0; j < K; ++j)
+        cols_params += (j ? ", const TIn" : "const TIn") + std::to_string(j) + " *__restrict__ col" + std::to_string(j);
+    src += "extern \"C\" __global__ void __launch_bounds__(256)\n"
+           "fq_jit_scan(" + cols_params + ", long long n, long long head, long long R,\n"
+           "            const u64 *__restrict__ bitmap, Consts c, Partial *parts) {\n"
+           "    Acc acc;\n    acc.sum = V(0); acc.mx = fq_max_id<V>(); acc.mn = fq_min_id<V>(); acc.cnt = 0; acc.flags = 0;\n";
+    gen_typed_loop(L, src);
+    src += R"JIT(
+    const Partial p = wg_reduce(acc);
+    if (threadIdx.x == 0) parts[blockIdx.x] = p;
+}
+)JIT";
+    return true;
+}
+
+// everything a typed source depends on: the widths (dtypes), the row group and
+// its prefetch, every cast (a K_CAST step with both types), every column reference
+std::string typed_shape_key(const Launch &L, bool chain, int dev) {
+    std::string k = "typed";
+    auto put = [&k](int32_t v) { k.append(reinterpret_cast<const char *>(&v), sizeof v); };
+    put(dev);
+    put(L.n_cols);
+    for (int j = 0; j < L.n_cols; ++j) put(L.cdt[j]);
+    put(L.group);
+    put(L.prefetch ? 1 : 0);
+    put(L.vdtype);
+    put((int32_t)L.mask);
+    put(L.block_mode ? 1 : 0);
+    put(chain ? 1 : 0);
+    put_pred_key(L.pred, k);
+    auto prog = [&put](const KProg &p) {
+        put(p.n);
+        for (int i = 0; i < p.n; ++i) {
+            put(p.s[i].code);
+            put(p.s[i].operand);
+            put(p.s[i].reversed);
+            put(p.s[i].dtype);
+            put(p.s[i].sdtype);
+            put(p.s[i].col);
+        }
+    };
+    if (chain) prog(L.val);
+    auto cols = [&put](const KProg &p) {
+        for (int i = 0; i < p.n; ++i) put(p.s[i].col);
+    };
+    put(L.pred.rhs_col);
+    cols(L.pred.lhs);
+    for (int l = 0; l < L.pred.n_leaves; ++l) {
+        put(L.pred.leaves[l].rhs_col);
+        cols(L.pred.leaves[l].lhs);
+    }
+    return k;
+}
+
 
 // ---------------------------------------------------------------------------
 // GROUP BY (fq_group_aggregate).  Same streaming loop as the scan; each
@@ -3457,6 +3998,7 @@ void jit_count_interp() { g_interp_launches += 1; }
 namespace {
 
 bool eligible(int32_t col_dtype, bool chain, const Launch &L) {
+    if (L.typed) return true;  // typed scans have no other kernel
     if (L.n_cols > 1) return true;  // scans over several columns have no other kernel
     if (!chain && L.pred.kind == FQ_PRED_NONE) return false;  // identity scans are already specialised
     return fqc::dtype_size(col_dtype) == 8;                      // expressions are 64-bit; narrow columns interpret
@@ -3482,14 +4024,14 @@ fq_status get_kernel(int32_t col_dtype, bool chain, const Launch &L, hipFunction
         (void)hipGetLastError();
         dev = -1;
     }
-    const std::string key = shape_key(L, col_dtype, chain, dev);
+    const std::string key = L.typed ? typed_shape_key(L, chain, dev) : shape_key(L, col_dtype, chain, dev);
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_cache.find(key);
     if (it == g_cache.end()) {
         Gen g;
         std::string src;
         Compiled c;
-        if (gen_source(L, col_dtype, chain, g, src)) {
+        if (L.typed ? gen_typed_source(L, chain, src) : gen_source(L, col_dtype, chain, g, src)) {
             fq_status s = compile(src, dev, c);
             if (s != FQ_OK) return s;
             c.ok = true;
@@ -3535,7 +4077,7 @@ fq_status jit_scan(int32_t col_dtype, bool chain, const Launch &L, bool *used, b
     long long n = L.n, head = L.head, R = L.block_rows;
     const uint64_t *bitmap = L.pred.bitmap;
     Partial *parts = L.parts;
-    if (L.n_cols > 1) {  // fq_jit_scan(col0 .. col{K-1}, n, head, R, ...); head < 0: the 8-byte path
+    if (L.n_cols > 1 || L.typed) {  // fq_jit_scan(col0 .. col{K-1}, n, head, R, ...); head < 0: the element path
         const void *cols[FQ_MAX_SCAN_COLS];
         void *args[FQ_MAX_SCAN_COLS + 6];
         int na = 0;

@@ -36,7 +36,45 @@ struct Launch {
     const void *cols[FQ_MAX_SCAN_COLS];
     int32_t cdt[FQ_MAX_SCAN_COLS];
     bool vec;
+    // fq_aggregate_typed with a narrow column, step or comparison (n_cols >= 1):
+    // a lane owns `group` consecutive rows of a tile of 256 * group rows and
+    // loads its group * width bytes of every column in one piece; `prefetch`:
+    // the next tile's pieces in flight.  vec: the columns share one phase
+    // (ptr / width) mod group (flat mode: `head` rows lead up to it; block mode:
+    // phase 0 and block_rows a multiple of group), else one row per lane.
+    bool typed;
+    int group;
+    bool prefetch;
 };
+
+// Row group of a typed scan over columns of the given widths: the largest
+// power of two G <= 16 with G * sum(w) <= 64 bytes per lane, so that a tile and
+// its prefetch stay within the single-column kernel's 128 bytes in flight.  A
+// column whose piece G * w would fall below a dword gives up the prefetch for
+// twice the bytes per tile instead (scalar narrow loads cost 2-2.5x a dword's),
+// when that lifts every piece to a dword (the first rule alone, and the
+// doubled group with its prefetch, measured slower and no faster: DESIGN.md
+// section 3, profiles/r09_typed_group_ab.json).
+inline void typed_group(const int32_t *cdt, int n_cols, int *group, bool *prefetch) {
+    int sum = 0, wmin = 8;
+    for (int j = 0; j < n_cols; ++j) {
+        const int w = fqc::dtype_size(cdt[j]);
+        sum += w;
+        wmin = w < wmin ? w : wmin;
+    }
+    auto fit = [sum](int bytes) {
+        int g = 16;
+        while (g > 1 && g * sum > bytes) g >>= 1;
+        return g;
+    };
+    const int g0 = fit(64), g1 = fit(128);
+    *group = g0;
+    *prefetch = true;
+    if (g0 * wmin < 4 && g1 * wmin >= 4) {
+        *group = g1;
+        *prefetch = false;
+    }
+}
 
 // Host lowering (fq_aggregate.hip): fq_expr -> KProg (res_dtype = result
 // type) and fq_pred -> KPred.
@@ -48,6 +86,12 @@ fq_status lower_pred(const fq_pred *pred, int32_t col_dtype, int64_t len, bool n
 fq_status lower_expr_cols(const fq_expr &e, const int32_t *cdt, int n_cols, KProg &out, int32_t &res_dtype);
 fq_status lower_pred_cols(const fq_pred *pred, const int32_t *cdt, int n_cols, int64_t len, bool need_data,
                           KPred &out);
+// Typed mode (fq_aggregate_typed): columns, steps and comparisons of any numeric
+// type; every step type is checked against numerical_coercion of its operands
+// and every cast is an explicit K_CAST.
+fq_status lower_expr_typed(const fq_expr &e, const int32_t *cdt, int n_cols, KProg &out, int32_t &res_dtype);
+fq_status lower_pred_typed(const fq_pred *pred, const int32_t *cdt, int n_cols, int64_t len, bool need_data,
+                           KPred &out);
 // Argument checks of the *_columns entry points: 1..FQ_MAX_SCAN_COLS columns of
 // equal len, each UINT64 / INT64 / FLOAT64 (`who` names the caller in the messages).
 fq_status check_cols(const fq_col *cols, int32_t n_cols, bool need_data, const char *who = "fq_aggregate_columns");

@@ -25,7 +25,7 @@ GPU_SYMBOLS = [
     "fq_tune_jit_dump_dir", "fq_filter_project_blocks_workspace_bytes", "fq_filter_project_blocks",
     "fq_blocks_compact_workspace_bytes", "fq_blocks_compact", "fq_aggregate_columns", "fq_jit_prepare_columns",
     "fq_filter_project_columns_workspace_bytes", "fq_filter_project_columns", "fq_filter_project_blocks_columns",
-    "fq_predicate_bitmap_columns", "fq_jit_prepare_project_columns",
+    "fq_predicate_bitmap_columns", "fq_jit_prepare_project_columns", "fq_aggregate_typed", "fq_jit_prepare_typed",
 ]
 
 
@@ -70,6 +70,10 @@ _protos = {
                                          C.c_uint32, vp, vp, C.c_size_t, vp]),
     "fq_jit_prepare_columns": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred), P(abi.fq_expr),
                                            C.c_uint32, P(C.c_int32)]),
+    "fq_aggregate_typed": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred), P(abi.fq_expr),
+                                       C.c_uint32, vp, vp, C.c_size_t, vp]),
+    "fq_jit_prepare_typed": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred), P(abi.fq_expr),
+                                         C.c_uint32, P(C.c_int32)]),
     "fq_arith_result_type": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, P(C.c_int32)]),
     "fq_arith": (C.c_int32, [C.c_int32, P(abi.fq_col), P(abi.fq_value), P(abi.fq_col),
                              P(abi.fq_value), P(abi.fq_col), vp, vp]),

@@ -210,6 +210,27 @@ def aggregate_columns(cols, block_rows=0, pred=None, value=None, mask=0xF, ws=No
     return state_from_device(aggregate_columns_async(cols, block_rows, pred, value, mask, ws, None, stream))
 
 
+def aggregate_typed_async(cols, block_rows=0, pred=None, value=None, mask=0xF, ws=None, out=None, stream=None):
+    """Launch fq_aggregate_typed over a list of DeviceColumns of one block, each
+    of any numeric dtype (expr.chain_columns / predicate_columns type the steps);
+    returns the device tensor holding the fq_agg_state."""
+    require_gpu()
+    ws = ws or Workspace(lib.fq_aggregate_workspace_bytes(cols[0].len if cols else 0))
+    if out is None:
+        out = torch.empty(48, dtype=torch.uint8, device="cuda")
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    check(lib.fq_aggregate_typed(arr, len(cols), block_rows, C.byref(pred) if pred is not None else None,
+                                 C.byref(value) if value is not None else None, mask,
+                                 C.c_void_p(out.data_ptr()), ws.ptr, ws.nbytes, _stream(stream)))
+    return out
+
+
+def aggregate_typed(cols, block_rows=0, pred=None, value=None, mask=0xF, ws=None, stream=None):
+    """Fused AggregatePartial over up to abi.MAX_SCAN_COLS columns of any
+    numeric dtypes of one device block -> host fq_agg_state."""
+    return state_from_device(aggregate_typed_async(cols, block_rows, pred, value, mask, ws, None, stream))
+
+
 def state_values(st):
     """fq_agg_state -> dict(sum, max, min, count, blocks, flags) of Python values."""
     dt = st.dtype
@@ -505,6 +526,16 @@ def jit_prepare_columns(dtypes, pred=None, value=None, mask=abi.AGG_SUM, block_r
     out = C.c_int32(0)
     check(lib.fq_jit_prepare_columns(arr, len(dtypes), int(block_rows), C.byref(pred) if pred is not None else None,
                                      C.byref(value) if value is not None else None, mask, C.byref(out)))
+    return bool(out.value)
+
+
+def jit_prepare_typed(dtypes, pred=None, value=None, mask=abi.AGG_SUM, block_rows=0, length=1 << 30, lengths=None):
+    """jit_prepare for fq_aggregate_typed: one dtype (any numeric) per column."""
+    lens = list(lengths) if lengths is not None else [int(length)] * len(dtypes)
+    arr = (abi.fq_col * max(len(dtypes), 1))(*[abi.fq_col(None, int(n), dt, 0) for dt, n in zip(dtypes, lens)])
+    out = C.c_int32(0)
+    check(lib.fq_jit_prepare_typed(arr, len(dtypes), int(block_rows), C.byref(pred) if pred is not None else None,
+                                   C.byref(value) if value is not None else None, mask, C.byref(out)))
     return bool(out.value)
 
 

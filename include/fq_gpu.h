@@ -135,7 +135,7 @@ typedef struct fq_step {
     int32_t op;       /* FQ_OP_*                                  */
     int32_t operand;  /* FQ_OPERAND_CONST / FQ_OPERAND_COLUMN     */
     int32_t reversed; /* 1: operand OP acc (scalar-array form)    */
-    int32_t dtype;    /* UINT64 / INT64 / FLOAT64                 */
+    int32_t dtype;    /* UINT64 / INT64 / FLOAT64 (fq_aggregate_typed: any numeric type) */
     uint64_t bits;    /* constant in `dtype` (fq_value encoding)  */
 } fq_step;
 
@@ -176,7 +176,7 @@ typedef struct fq_pred_tree {
 typedef struct fq_pred {
     int32_t kind;
     int32_t cmp;         /* FQ_CMP_*  (already flipped for scalar-array forms)   */
-    int32_t cmp_dtype;   /* equal_coercion type: UINT64 / INT64 / FLOAT64         */
+    int32_t cmp_dtype;   /* equal_coercion type: UINT64 / INT64 / FLOAT64 (fq_aggregate_typed: any numeric) */
     int32_t rhs_operand; /* FQ_OPERAND_CONST / FQ_OPERAND_COLUMN                  */
     uint64_t rhs_bits;   /* constant in cmp_dtype                                */
     fq_expr lhs;         /* lhs.out_dtype must equal cmp_dtype                   */
@@ -268,6 +268,41 @@ fq_status fq_aggregate(const fq_col *col, int64_t block_rows, const fq_pred *pre
 fq_status fq_aggregate_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows,
                                const fq_pred *pred, const fq_expr *value, uint32_t agg_mask,
                                fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream);
+
+/* ---- The same scan over columns, steps and comparisons of any numeric type ----
+ * (numerical_coercion ranges over all ten numeric types, data_type.rs:27-87: a
+ * host brings dates as Int32, quantities as UInt8, discounts as Float32).
+ * cols[0..n_cols) have equal len and any numeric dtype each; the column
+ * references, workspace, block_rows, predicate kinds, flags, the fixed-order
+ * fold and the error order are fq_aggregate_columns'.  Every fq_step.dtype,
+ * cmp_dtype and out_dtype may be any numeric type, and must be the type that
+ * numerical_coercion / equal_coercion yields for its operands (FQ_E_INVALID
+ * otherwise; for a constant operand: a type at or before acc's in the
+ * coercion order).  A step or comparison in type T sees acc, a column operand
+ * and a popped stack value cast to T as arrow 2.0 casts: an integer outside
+ * T's range is arrow's null, FQ_STATE_CAST_NULL on a live row; integer ->
+ * float rounds to nearest; Float32 -> Float64 is exact.  A constant arrives
+ * already in the step's type (fq_value encoding).  Integer steps of width w
+ * wrap modulo 2^w, '/' and '%' truncate (T::MIN / -1 wraps to T::MIN,
+ * T::MIN % -1 = 0), Float32 steps round to binary32 one step at a time ('%'
+ * is fmodf); a zero divisor on a live row sets FQ_STATE_DIV_ZERO.  The state
+ * is in the value's type V with the encoding of a scan over a single narrow
+ * column: integer sums wrap at V's width and are stored sign- or
+ * zero-extended, Float32 accumulates in binary32 and is stored widened.
+ *
+ * When every column, step and comparison type is 64-bit the call IS
+ * fq_aggregate_columns.  Any other shape runs on hipRTC-specialised kernels
+ * only, whatever min_rows says (FQ_E_UNSUPPORTED with FQ_JIT_OFF or without
+ * hipRTC).  fq_jit_prepare_typed compiles (and caches) the kernel of a call
+ * shape ahead of the first scan (the columns' data may be NULL: they then
+ * count as aligned); without a GPU the generated source is compiled for
+ * gfx950 only to validate it.                                               */
+fq_status fq_aggregate_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                             const fq_pred *pred, const fq_expr *value, uint32_t agg_mask,
+                             fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream);
+fq_status fq_jit_prepare_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                               const fq_pred *pred, const fq_expr *value, uint32_t agg_mask,
+                               int32_t *specialised);
 
 /* ---- ArithmeticFunction::eval (data_array_arithmetic.rs:14-55) ----
  * Exactly one of {lhs, lhs_scalar} and one of {rhs, rhs_scalar} is non-NULL.

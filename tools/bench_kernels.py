@@ -10,6 +10,7 @@ checked against numpy on a prefix.  Prints one JSON document.
 usage: python tools/bench_kernels.py [--rows 1.25e9] [--reps 10] > gpurun_out/kernels.json
        python tools/bench_kernels.py --only q6 [--q6-rows 134217728] [--reps 20]   (the q6 lines alone)
        python tools/bench_kernels.py --only pcols [--q6-rows 134217728] [--reps 20]   (Filter -> Projection over 3 columns)
+       python tools/bench_kernels.py --only typed [--q6-rows 134217728] [--reps 20]   (the Q6 shape over narrow columns)
 """
 import argparse
 import ctypes as C
@@ -261,18 +262,153 @@ def pcols_lines(n, reps, st, res):
                 "gate_fused_below_unfused": bool(f_blk < u and f_con < u)})
 
 
+def typed_lines(n, reps, st, res):
+    """sum(price * discount) WHERE shipdate < k and quantity < q over price Float64, discount Float32,
+    shipdate Int32, quantity UInt8 (17 B/row, about 3/8 of the rows kept): ONE fq_aggregate_typed scan,
+    beside -- in the same process -- the same statement over the four columns widened to 64 bits through
+    fq_aggregate_columns (32 B/row) and the unfused path (what engine/functions.cpp
+    AggregatorFunction::summarize runs with the JIT off, the only path for this block before the typed scan:
+    two fq_compare, fq_logic, a bitmap probe scan, fq_filter_compact of every column, fq_arith on the kept
+    rows, an identity scan).  Every launch event-timed."""
+    from fq_amd.expr import Col, chain_columns, load, pred_tree_columns
+    F64, F32, I32, U8, I64, U64 = (abi.DT_FLOAT64, abi.DT_FLOAT32, abi.DT_INT32, abi.DT_UINT8, abi.DT_INT64,
+                                   abi.DT_UINT64)
+    K, Q = 9950, 26  # shipdate in [8000, 10600): 3/4 below K; quantity in [1, 50]: 1/2 below Q
+    g = torch.Generator(device="cuda")
+    g.manual_seed(9)
+    t_price = torch.rand(n, dtype=torch.float64, device="cuda", generator=g) * 999.0 + 1.0
+    t_disc = torch.randint(0, 11, (n,), device="cuda", generator=g).to(torch.float32) / 100.0
+    t_ship = torch.randint(8000, 10600, (n,), dtype=torch.int32, device="cuda", generator=g)
+    t_qty = torch.randint(1, 51, (n,), dtype=torch.uint8, device="cuda", generator=g)
+
+    def column(t, dt):
+        return ops.DeviceColumn(t.view(torch.uint8), n, dt)
+
+    narrow = [column(t_price, F64), column(t_disc, F32), column(t_ship, I32), column(t_qty, U8)]
+    ndts = [F64, F32, I32, U8]
+    wide_t = [t_price, t_disc.to(torch.float64), t_ship.to(torch.int64), t_qty.to(torch.int64)]
+    wdts = [F64, F64, I64, U64]
+    wide = [column(t, dt) for t, dt in zip(wide_t, wdts)]
+
+    def program(dts, kt, qt):
+        pred = pred_tree_columns(dts, [([load(2)], "<", (K, kt)), ([load(3)], "<", (Q, qt))], [0, 1, "and"])
+        value, vdt = chain_columns(dts, [("*", Col(1))])
+        assert vdt == F64
+        return pred, value
+
+    npred, nvalue = program(ndts, "Int32", "UInt8")
+    wpred, wvalue = program(wdts, "Int64", "UInt64")
+    ncols = (abi.fq_col * 4)(*[c.col() for c in narrow])
+    wcols = (abi.fq_col * 4)(*[c.col() for c in wide])
+    aws = ops.Workspace(lib.fq_aggregate_workspace_bytes(n))
+    dst = torch.empty(48, dtype=torch.uint8, device="cuda")
+    SC = abi.AGG_SUM | abi.AGG_COUNT
+
+    def rec(name, ts, nbytes, note=""):
+        ms = statistics.median(ts)
+        gbps = nbytes / (ms * 1e-3) / 1e9
+        res.append({"kernel": name, "ms": ms, "ms_min": min(ts), "ms_max": max(ts), "reps": len(ts),
+                    "algorithmic_bytes": nbytes, "achieved_gbps": gbps, "frac_of_peak": gbps / PEAK, "note": note})
+        print("%-58s %8.3f ms [%.3f .. %.3f]  %7.0f GB/s  %4.1f %%" % (name, ms, min(ts), max(ts), gbps,
+                                                                     100 * gbps / PEAK), file=sys.stderr)
+        return ts
+
+    keep = (t_ship < K) & (t_qty < Q)
+    kept_rows = int(keep.sum())
+    prod = t_price[keep] * t_disc[keep].to(torch.float64)
+    want, scale = float(prod.sum()), float(prod.abs().sum())
+    del prod
+
+    def verify(what):
+        got = ops.state_from_device(dst)
+        s = ops.state_values(got)["sum"]
+        assert got.count == kept_rows and got.flags == 0 and abs(s - want) <= 1e-12 * scale, (what, got.count, kept_rows, s, want)
+
+    def typed(br):
+        check(lib.fq_aggregate_typed(ncols, 4, br, C.byref(npred), C.byref(nvalue), SC, C.c_void_p(dst.data_ptr()),
+                                     aws.ptr, aws.nbytes, st))
+
+    def widened(br):
+        check(lib.fq_aggregate_columns(wcols, 4, br, C.byref(wpred), C.byref(wvalue), SC, C.c_void_p(dst.data_ptr()),
+                                       aws.ptr, aws.nbytes, st))
+
+    t_flat = rec("typed q6 sum(price*discount), f64 f32 i32 u8 columns", timed_all(lambda: typed(0), reps), 17 * n,
+                 "fq_aggregate_typed, one DataBlock (block_rows 0): flat scan, 17 B/row")
+    verify("typed flat")
+    t_blk = rec("typed q6, 10,000-row blocks", timed_all(lambda: typed(10000), reps), 17 * n,
+                "fq_aggregate_typed, block mode: one wave per reference block")
+    verify("typed blocks")
+    w_flat = rec("widened q6, 4 64-bit columns", timed_all(lambda: widened(0), reps), 32 * n,
+                 "fq_aggregate_columns over the columns widened to 64 bits, flat scan, 32 B/row")
+    verify("widened flat")
+    w_blk = rec("widened q6, 4 64-bit columns, 10,000-row blocks", timed_all(lambda: widened(10000), reps), 32 * n,
+                "fq_aggregate_columns, block mode")
+    verify("widened blocks")
+
+    # the unfused path for the same statement over the narrow columns
+    bm1, bm2, bm = (ops.empty_column(n, abi.DT_BOOLEAN) for _ in range(3))
+    kept_cols = [ops.empty_column(n, dt) for dt in ndts]
+    prod_col = ops.empty_column(n, F64)
+    fws = ops.Workspace(lib.fq_filter_workspace_bytes(n))
+    kv, qv = abi.fq_value(I32, 1, K), abi.fq_value(U8, 1, Q)
+    kept = C.c_int64(0)
+    pb = abi.fq_pred()
+    pb.kind = abi.PRED_BITMAP
+    pb.bitmap = bm.ptr
+    sc, qc = narrow[2].col(), narrow[3].col()
+
+    def unfused():
+        lt = abi.CMP_BY_SYM["<"]
+        check(lib.fq_compare(lt, C.byref(sc), None, None, C.byref(kv), C.c_void_p(bm1.ptr), n, None, st))
+        check(lib.fq_compare(lt, C.byref(qc), None, None, C.byref(qv), C.c_void_p(bm2.ptr), n, None, st))
+        check(lib.fq_logic(0, C.c_void_p(bm1.ptr), C.c_void_p(bm2.ptr), C.c_void_p(bm.ptr), n, st))
+        check(lib.fq_aggregate(C.byref(sc), 0, C.byref(pb), None, SC, C.c_void_p(dst.data_ptr()), aws.ptr, aws.nbytes, st))
+        for src, out in zip(narrow, kept_cols):
+            c = src.col()
+            check(lib.fq_filter_compact(C.byref(c), C.c_void_p(bm.ptr), C.c_void_p(out.ptr), C.byref(kept), fws.ptr,
+                                        fws.nbytes, st))
+        m = kept.value
+        lc = abi.fq_col(C.c_void_p(kept_cols[0].ptr), m, F64, 0)
+        rc = abi.fq_col(C.c_void_p(kept_cols[1].ptr), m, F32, 0)
+        oc = abi.fq_col(C.c_void_p(prod_col.ptr), m, F64, 0)
+        check(lib.fq_arith(abi.OP_BY_SYM["*"], C.byref(lc), None, C.byref(rc), None, C.byref(oc), None, st))
+        check(lib.fq_aggregate(C.byref(oc), 0, None, None, SC, C.c_void_p(dst.data_ptr()), aws.ptr, aws.nbytes, st))
+
+    ops.jit_config(abi.JIT_OFF, 0)
+    try:
+        ts = timed_all(unfused, reps)
+    finally:
+        ops.jit_config(abi.JIT_AUTO, 1 << 22)
+    m = kept.value
+    assert m == kept_rows
+    verify("unfused")
+    bits = n // 8
+    moved = (4 * n + bits) + (n + bits) + 3 * bits + (4 * n + bits) + (17 * n + 4 * bits + 17 * m) + 20 * m + 8 * m
+    u = rec("typed q6 unfused: 2 compare, and, probe, 4 compactions, arith, scan", ts, moved,
+            "this block with the JIT off (the parent's only path); includes fq_filter_compact's host syncs; "
+            "bytes = what the path moves")
+    med = statistics.median
+    res.append({"typed_q6": {
+        "rows": n, "kept_rows": kept_rows, "bytes_per_row": {"typed": 17, "widened": 32},
+        "typed_tb_per_s": {"flat": 17 * n / (med(t_flat) * 1e-3) / 1e12, "block_mode": 17 * n / (med(t_blk) * 1e-3) / 1e12},
+        "unfused_over_typed": {"flat": med(u) / med(t_flat), "block_mode": med(u) / med(t_blk)},
+        "widened_over_typed": {"flat": med(w_flat) / med(t_flat), "block_mode": med(w_blk) / med(t_blk)},
+        "gate_typed_below_unfused_non_overlapping": bool(max(t_flat) < min(u) and max(t_blk) < min(u)),
+        "typed_below_widened": {"flat": bool(med(t_flat) < med(w_flat)), "block_mode": bool(med(t_blk) < med(w_blk))}}})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=float, default=1.25e9)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--only", choices=["q6", "pcols"], default=None, help="run only the named group of lines")
+    ap.add_argument("--only", choices=["q6", "pcols", "typed"], default=None, help="run only the named group of lines")
     ap.add_argument("--q6-rows", type=float, default=float(1 << 27))
     args = ap.parse_args()
     n = int(args.rows)
     st = ops._stream()
     res = []
-    if args.only in ("q6", "pcols"):
-        (q6_lines if args.only == "q6" else pcols_lines)(int(args.q6_rows), args.reps, st, res)
+    if args.only in ("q6", "pcols", "typed"):
+        {"q6": q6_lines, "pcols": pcols_lines, "typed": typed_lines}[args.only](int(args.q6_rows), args.reps, st, res)
         print(json.dumps({"rows": int(args.q6_rows), "peak_gbps": PEAK, "device": torch.cuda.get_device_name(0),
                           "kernels": res}, indent=1))
         return
@@ -449,6 +585,7 @@ def main():
         "includes the table init (4 GB)")
 
     q6_lines(int(args.q6_rows), args.reps, st, res)
+    typed_lines(int(args.q6_rows), args.reps, st, res)
 
     print(json.dumps({"rows": n, "peak_gbps": PEAK, "device": torch.cuda.get_device_name(0),
                       "kernels": res}, indent=1))

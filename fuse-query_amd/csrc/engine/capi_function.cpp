@@ -334,11 +334,15 @@ fq_status fq_functions_eval(fq_engine *e, fq_function *const *fs, int32_t n, con
                 const int64_t kept = out.layout ? out.layout->rows : out.num_rows();
                 for (int32_t i = 0; i < n; ++i) out_dtypes[i] = out.columns[(size_t)i].dtype;
                 *out_len = kept;
-                *out_bytes = blocks ? full : (size_t)kept * 8;
+                // every output at its own width: the widest one's kept rows are what a buffer needs
+                size_t widest = 0;
+                for (int32_t i = 0; i < n; ++i) widest = std::max(widest, (size_t)fq::dtype_size(out_dtypes[i]));
+                *out_bytes = blocks ? full : (size_t)kept * widest;
                 *fused = one_kernel ? 1 : 0;  // 0: the filter's bitmap came from its own kernels first
                 if (!direct) {
                     if (*out_bytes > cap) throw fq::FQException(FQ_E_INVALID, "fq_functions_eval: output buffers too small");
-                    for (int32_t i = 0; i < n; ++i) copy_out(out.columns[(size_t)i], d_out[i], *out_bytes);
+                    for (int32_t i = 0; i < n; ++i)
+                        copy_out(out.columns[(size_t)i], d_out[i], (size_t)kept * (size_t)fq::dtype_size(out_dtypes[i]));
                 }
                 ctx.sync();
                 return;
@@ -372,10 +376,10 @@ fq_status fq_functions_eval(fq_engine *e, fq_function *const *fs, int32_t n, con
             const std::vector<fq::Column> cols = eval_each(fs, n, plain, ctx);
             for (int32_t i = 0; i < n; ++i) {
                 const fq::Column &c = cols[(size_t)i];
-                if (fq::dtype_size(c.dtype) != 8 || c.dtype == FQ_DT_BOOLEAN)
-                    throw fq::FQException(FQ_E_UNSUPPORTED, "fq_functions_eval: block geometry holds 64-bit outputs only");
+                if (c.dtype == FQ_DT_BOOLEAN || fq::dtype_size(c.dtype) < 1 || fq::dtype_size(c.dtype) > 8)
+                    throw fq::FQException(FQ_E_UNSUPPORTED, "fq_functions_eval: block geometry holds numeric outputs only");
                 out_dtypes[i] = c.dtype;
-                copy_out(c, (char *)d_out[i] + (size_t)(k * B) * 8, column_bytes(c));
+                copy_out(c, (char *)d_out[i] + (size_t)(k * B) * (size_t)fq::dtype_size(c.dtype), column_bytes(c));
             }
             counts[(size_t)k] = plain.num_rows();
             kept += plain.num_rows();

@@ -690,13 +690,16 @@ FunctionRef function_factory(const std::string &name, std::vector<FunctionRef> a
 // ---------------------------------------------------------------------------
 // The device columns a fused row kernel reads, in `cols`' order; false when one
 // is not 64-bit device data (or, with several, not UInt64 / Int64 / Float64).
+// typed: the *_typed entry points read device columns of any numeric type.
 static bool fused_device_columns(const DataBlock &b, const FusedColumns &cols, std::vector<Column> &out,
-                                 fq_col (&abi)[FQ_MAX_SCAN_COLS]) {
+                                 fq_col (&abi)[FQ_MAX_SCAN_COLS], bool typed = false) {
     out.clear();
     for (size_t j = 0; j < cols.names.size(); ++j) {
         const Column &c = b.column_by_name(cols.names[j]);
-        if (!c.on_device() || dtype_size(c.dtype) != 8 || c.dtype == FQ_DT_BOOLEAN) return false;
-        if (cols.names.size() > 1 && !is_chain_dtype(c.dtype)) return false;
+        if (typed ? !c.on_device() || !dtype_is_numeric(c.dtype)
+                  : !c.on_device() || dtype_size(c.dtype) != 8 || c.dtype == FQ_DT_BOOLEAN)
+            return false;
+        if (!typed && cols.names.size() > 1 && !is_chain_dtype(c.dtype)) return false;
         out.push_back(c);
         abi[j] = c.abi();
     }
@@ -710,15 +713,20 @@ static bool fused_device_columns(const DataBlock &b, const FusedColumns &cols, s
 static bool fused_predicate_bitmap(Function &pred, const DataBlock &b, ExecCtx &ctx, Column &out) {
     FusedPred fp;
     FusedColumns cols;
+    cols.typed = tree_fusion_enabled();  // with the JIT on: columns and comparisons of any numeric type
     if (!b.schema || !pred.to_pred(*b.schema, fp, &cols)) return false;
+    // a narrow column or comparison: fq_predicate_bitmap_typed, when its lowering has room for the casts
+    bool typed = cols.typed && pred_is_narrow(fp);
+    for (DataType d : cols.dtypes) typed = typed || (cols.typed && !is_chain_dtype(d));
+    if (typed && !fqk::typed_project_fits(cols.dtypes.data(), (int32_t)cols.names.size(), fp.get(), nullptr, 0)) return false;
     std::vector<Column> cs;
     fq_col ics[FQ_MAX_SCAN_COLS];
-    if (!fused_device_columns(b, cols, cs, ics)) return false;
+    if (!fused_device_columns(b, cols, cs, ics, typed)) return false;
     const Column &c = cs[0];
     Column bm = Column::device(FQ_DT_BOOLEAN, c.len, ctx.stream());
     auto flag = DeviceBuffer::alloc(sizeof(uint32_t), ctx.stream());
-    const fq_status st = fq_predicate_bitmap_columns(ics, (int32_t)cs.size(), fp.get(), (uint64_t *)bm.dptr(),
-                                                     (uint32_t *)flag->ptr, ctx.stream());
+    const fq_status st = (typed ? fq_predicate_bitmap_typed : fq_predicate_bitmap_columns)(
+        ics, (int32_t)cs.size(), fp.get(), (uint64_t *)bm.dptr(), (uint32_t *)flag->ptr, ctx.stream());
     if (st == FQ_E_UNSUPPORTED) return false;  // no hipRTC / JIT off / shape outside it: per node (same errors)
     check_fq(st);
     out = bm;
@@ -833,8 +841,10 @@ DataBlock materialize(const DataBlock &b, ExecCtx &ctx) {
 // event pair around every launch, the second with one span per query.
 static bool project_blocks(const DataBlock &b, const std::vector<Column> &cs, const fq_pred *pred, std::vector<fq_expr> &exprs,
                            std::vector<Column> &outs, std::vector<void *> &ptrs, const SchemaRef &schema, ExecCtx &ctx,
-                           DataBlock &out, LaunchSpan *span, const ProjectInto *into) {
+                           DataBlock &out, LaunchSpan *span, const ProjectInto *into, bool typed) {
     const Column &c = cs[0];
+    // a narrow column, step, comparison or output: fq_filter_project_blocks_typed's launch
+    const auto enqueue = typed ? fqk::filter_project_blocks_enqueue_typed : fqk::filter_project_blocks_enqueue_columns;
     const int32_t n_cols = (int32_t)cs.size();
     const int64_t n = c.len, B = b.sub_block_rows;
     const int64_t nb = n <= B ? 1 : (n + B - 1) / B;
@@ -867,9 +877,8 @@ static bool project_blocks(const DataBlock &b, const std::vector<Column> &cs, co
         none[j] = ic[j] = cs[(size_t)j].abi();
         none[j].len = 0;
     }
-    fq_status st = fqk::filter_project_blocks_enqueue_columns(none, n_cols, B, pred, exprs.data(), (int32_t)exprs.size(),
-                                                              ptrs.data(), nullptr, res, nullptr, nullptr, 0, nullptr,
-                                                              nullptr, ctx.stream());
+    fq_status st = enqueue(none, n_cols, B, pred, exprs.data(), (int32_t)exprs.size(), ptrs.data(), nullptr, res, nullptr,
+                           nullptr, 0, nullptr, nullptr, ctx.stream());
     if (st == FQ_E_UNSUPPORTED) return false;
     check_fq(st);
     hipEvent_t done = ctx.res->take_sync_event();
@@ -879,11 +888,9 @@ static bool project_blocks(const DataBlock &b, const std::vector<Column> &cs, co
         // this worker's last hand-off has landed (the pipe waited for it); an
         // empty block launches nothing, so its words must read 0 kept rows
         res[0] = res[1] = 0;
-        st = fqk::filter_project_blocks_enqueue_columns(ic, n_cols, B, pred, exprs.data(), (int32_t)exprs.size(),
-                                                        ptrs.data(), d_counts, res,
-                                                        resident ? ctx.res->project_dres : nullptr,
-                                                        resident ? ctx.res->project_ws : ws->ptr,
-                                                        fq_filter_project_blocks_workspace_bytes(), e0, e1, ctx.stream());
+        st = enqueue(ic, n_cols, B, pred, exprs.data(), (int32_t)exprs.size(), ptrs.data(), d_counts, res,
+                     resident ? ctx.res->project_dres : nullptr, resident ? ctx.res->project_ws : ws->ptr,
+                     fq_filter_project_blocks_workspace_bytes(), e0, e1, ctx.stream());
         if (st == FQ_OK) check_hip(hipEventRecord(done, ctx.stream()), "hipEventRecord");  // after the result words
     }
     if (st == FQ_OK) {
@@ -906,8 +913,11 @@ static bool project_blocks(const DataBlock &b, const std::vector<Column> &cs, co
     S.project_launches++;
     S.project_rows += (uint64_t)n;
     S.project_kept += (uint64_t)kept;
-    // every column read once: 8 bytes per row per column
-    S.project_bytes += (uint64_t)n * (uint64_t)dtype_size(c.dtype) * (uint64_t)n_cols + (uint64_t)kept * 8 * (uint64_t)outs.size();
+    // every column read once and every kept row's outputs written, each at its own width
+    uint64_t row_bytes = 0, out_bytes = 0;
+    for (const Column &ci : cs) row_bytes += (uint64_t)dtype_size(ci.dtype);
+    for (const Column &o : outs) out_bytes += (uint64_t)dtype_size(o.dtype);
+    S.project_bytes += (uint64_t)n * row_bytes + (uint64_t)kept * out_bytes;
     out = DataBlock{};
     out.schema = schema;
     out.sub_block_rows = B;
@@ -920,39 +930,53 @@ static bool project_blocks(const DataBlock &b, const std::vector<Column> &cs, co
 // ProjectionTransform over a block with a pending filter (or none): when every
 // projected expression is a chain or tree over up to FQ_MAX_SCAN_COLS 64-bit
 // device columns, one fq_filter_project_columns call compacts and evaluates
-// them together.  The columns are numbered like AggFusion's: the filter's
+// them together; with a narrow column, step, comparison or output among them
+// (and the JIT on) one fq_filter_project_typed call, its outputs allocated at
+// their own widths.  The columns are numbered like AggFusion's: the filter's
 // first, then the expressions' by first appearance.  A filter that does not
 // fuse (or would be the fifth column) has its bitmap evaluated first.  false:
-// not fusable (a fifth column, a ninth step, a narrow or host column, the JIT
-// off), the caller materialises + evaluates.
+// not fusable (a fifth column, a ninth step, a host column, a Boolean output, a
+// Constant, a typed chain whose casts leave the lowered program no room, the
+// JIT off), the caller materialises + evaluates.
 bool project_fused(const DataBlock &b, const std::vector<FunctionRef> &funcs, const SchemaRef &schema, ExecCtx &ctx,
                    DataBlock &out, bool block_stream, LaunchSpan *span, const ProjectInto *into, bool *one_kernel) {
     if (funcs.empty() || funcs.size() > FQ_MAX_PROJECT || !b.schema || b.columns.empty()) return false;
     // the expressions over the filter's columns; false: a chain does not fuse
+    // (with the JIT on -- typed_on -- the columns, steps, comparisons and
+    // outputs may have any numeric type: the *_typed entry points; Boolean
+    // outputs and Constants never fuse)
+    const bool typed_on = tree_fusion_enabled();
     auto collect = [&](FusedColumns &cols, std::vector<FusedChain> &chains) {
         for (size_t j = 0; j < funcs.size(); ++j) {
             if (!funcs[j]->to_chain(*b.schema, chains[j], &cols)) return false;
-            if (dtype_size(chains[j].out_dtype) != 8) return false;
+            if (typed_on ? !dtype_is_numeric(chains[j].out_dtype) : dtype_size(chains[j].out_dtype) != 8) return false;
         }
         return true;
     };
     std::vector<FusedChain> chains(funcs.size());
     FusedColumns cols;
+    cols.typed = typed_on;
     FusedPred fp;
     bool pred_fused = b.filter && b.filter->to_pred(*b.schema, fp, &cols);
-    if (!pred_fused) cols = FusedColumns{};
+    if (!pred_fused) cols = FusedColumns{}, cols.typed = typed_on;
     if (!collect(cols, chains)) {
         if (!pred_fused) return false;
         pred_fused = false;  // without the filter's columns the expressions may still fit
         cols = FusedColumns{};
+        cols.typed = typed_on;
         if (!collect(cols, chains)) return false;
     }
+    // a narrow column, step, comparison or output: the block goes to the typed entry points
+    bool typed = pred_fused && pred_is_narrow(fp);
+    for (DataType d : cols.dtypes) typed = typed || !is_chain_dtype(d);
+    for (auto &fc : chains) typed = typed || expr_is_narrow(fc.expr) || !is_chain_dtype(fc.out_dtype);
+    typed = typed && typed_on;
     bool computes = false;
     for (auto &fc : chains) computes |= fc.expr.n_steps > 0;
     if (!b.filter && !computes && !into) return false;  // plain column references: zero-copy in the unfused path
     std::vector<Column> cs;
     fq_col ics[FQ_MAX_SCAN_COLS];
-    if (!fused_device_columns(b, cols, cs, ics)) return false;
+    if (!fused_device_columns(b, cols, cs, ics, typed)) return false;
     const int32_t n_cols = (int32_t)cs.size();
     fq_jit_stats js{};
     if (fq_jit_get_stats(&js) != FQ_OK || js.mode == FQ_JIT_OFF || js.available == 0) return false;
@@ -962,6 +986,10 @@ bool project_fused(const DataBlock &b, const std::vector<FunctionRef> &funcs, co
         if (n_cols > 1 && !fc.with_load(e)) return false;  // no step left for FQ_OP_LOAD
         exprs.push_back(e);
     }
+    // (a cast per change of acc's type may leave a lowered program no room: unfused then)
+    if (typed && !fqk::typed_project_fits(cols.dtypes.data(), n_cols, pred_fused ? fp.get() : nullptr, exprs.data(),
+                                          (int32_t)exprs.size()))
+        return false;
     fq_pred bp{};
     const fq_pred *pred = nullptr;
     Column bm;
@@ -985,13 +1013,17 @@ bool project_fused(const DataBlock &b, const std::vector<FunctionRef> &funcs, co
                             : Column::device(chains[j].out_dtype, n, ctx.stream()));
         ptrs.push_back(outs.back().dptr());
     }
-    if (into ? into->d_counts != nullptr : (block_stream && pred && b.sub_block_rows >= FQ_PROJECT_MIN_BLOCK_ROWS))
-        return project_blocks(b, cs, pred, exprs, outs, ptrs, schema, ctx, out, span, into);
-    const size_t wsb = fq_filter_project_columns_workspace_bytes(n, n_cols);
+    // (a block-stream layout of the engine's own holds 64-bit columns: narrow outputs take that geometry only
+    // into a caller's buffers)
+    if (into ? into->d_counts != nullptr
+             : (block_stream && !typed && pred && b.sub_block_rows >= FQ_PROJECT_MIN_BLOCK_ROWS))
+        return project_blocks(b, cs, pred, exprs, outs, ptrs, schema, ctx, out, span, into, typed);
+    const size_t wsb = typed ? fq_filter_project_typed_workspace_bytes(n, ics, n_cols)
+                             : fq_filter_project_columns_workspace_bytes(n, n_cols);
     auto ws = DeviceBuffer::alloc(wsb, ctx.stream());
     int64_t kept = 0;
-    const fq_status st = fq_filter_project_columns(ics, n_cols, pred, exprs.data(), (int32_t)exprs.size(), ptrs.data(),
-                                                   &kept, ws->ptr, wsb, ctx.stream());
+    const fq_status st = (typed ? fq_filter_project_typed : fq_filter_project_columns)(
+        ics, n_cols, pred, exprs.data(), (int32_t)exprs.size(), ptrs.data(), &kept, ws->ptr, wsb, ctx.stream());
     if (st == FQ_E_UNSUPPORTED) return false;  // the unfused path evaluates it (and raises what the reference does)
     check_fq(st);
     out = DataBlock{};

@@ -1084,7 +1084,7 @@ static const char *kTypedNeedsJit =
     "scans over narrow or mixed-width columns run on the hipRTC kernels only (FQ_JIT is off or hipRTC is "
     "unavailable)";
 
-static fq_status check_cols_typed(const fq_col *cols, int32_t n_cols, bool need_data, const char *who) {
+fq_status check_cols_typed(const fq_col *cols, int32_t n_cols, bool need_data, const char *who) {
     const std::string W = std::string(who) + ": ";
     if (!cols) return fqc::fail(FQ_E_INVALID, W + "NULL argument");
     if (n_cols < 1 || n_cols > FQ_MAX_SCAN_COLS)
@@ -1115,7 +1115,7 @@ static bool expr_is_64(const fq_expr *e) {
             return false;
     return true;
 }
-static bool call_is_64(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *value) {
+bool call_is_64(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *value) {
     for (int j = 0; j < n_cols; ++j)
         if (!is_chain_dtype(cols[j].dtype)) return false;
     if (!expr_is_64(value)) return false;

@@ -77,7 +77,18 @@ fq_status filter_project_blocks_enqueue_columns(const fq_col *cols, int32_t n_co
                                                 void *const *d_out, int64_t *d_counts, uint64_t *h_result,
                                                 uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
                                                 void *ev_end, void *stream);
+// the same for fq_filter_project_blocks_typed: columns, steps, comparisons and
+// outputs of any numeric type (all 64-bit: the call above)
+fq_status filter_project_blocks_enqueue_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                                              const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                              void *const *d_out, int64_t *d_counts, uint64_t *h_result,
+                                              uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
+                                              void *ev_end, void *stream);
 fq_status filter_project_blocks_result(const uint64_t *h_result, int64_t *out_len);
+// Whether the typed projection's lowering takes this predicate and these
+// values over columns of dtypes cdt: the dry run of typed_scan_fits for
+// fq_filter_project_typed (false: a chain whose casts leave no room).
+bool typed_project_fits(const int32_t *cdt, int32_t n_cols, const fq_pred *pred, const fq_expr *values, int32_t n_out);
 // Whether fq_aggregate_typed's lowering takes this predicate and value over
 // columns of dtypes cdt (fq_aggregate.hip): a dry run that launches nothing.
 // Every change of acc's type costs a lowered step for its cast, so a chain of

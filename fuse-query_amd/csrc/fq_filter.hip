@@ -479,9 +479,11 @@ struct ProjWs {
     int64_t ntiles;
 };
 
-ProjWs proj_ws(void *d_ws, int64_t n, int n_cols = 1) {
+// tile: the look-back tile's rows (0: the 64-bit kernels' over n_cols columns)
+ProjWs proj_ws(void *d_ws, int64_t n, int n_cols = 1, int64_t tile = 0) {
     ProjWs w;
-    w.ntiles = (n + select_tile_rows(n_cols) - 1) / select_tile_rows(n_cols);
+    if (tile <= 0) tile = select_tile_rows(n_cols);
+    w.ntiles = (n + tile - 1) / tile;
     w.total = (uint64_t *)d_ws;
     w.flags = (uint32_t *)(w.total + 1);
     w.ticket = (uint32_t *)(w.total + 2);
@@ -573,16 +575,72 @@ fq_status check_one_col_refs(const fq_col *col, const fq_pred *pred, const fq_ex
     return lower_pred_cols(pred, &col->dtype, 1, col->len, false, kd);
 }
 
+// The load geometry of a typed launch (after its outputs are known).
+void set_typed_geometry(ProjLaunch &P) {
+    int wout = 1;
+    for (int j = 0; j < P.n_out; ++j) wout = std::max(wout, fqc::dtype_size(P.dtypes[j]));
+    typed_project_geometry(P.cdt, P.n_cols, wout, &P.rows, &P.group);
+}
+
+// every column, step, comparison and output type of a *_typed call is 64-bit:
+// the call is its *_columns twin
+bool project_call_is_64(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *values, int32_t n_out) {
+    if (!call_is_64(cols, n_cols, pred, nullptr)) return false;
+    if (n_out < 0 || n_out > FQ_MAX_PROJECT || (n_out > 0 && !values)) return false;  // the typed lowering reports it
+    for (int j = 0; j < n_out; ++j)
+        if (!call_is_64(cols, n_cols, nullptr, &values[j]) ||
+            (values[j].n_steps > 0 && fqc::dtype_size(values[j].out_dtype) != 8))
+            return false;
+    return true;
+}
+
+// lower_projection_cols for the *_typed entry points: n_cols >= 1 checked
+// columns, steps, comparisons and outputs of any numeric type (each checked
+// against the coercion of its operands), an output buffer aligned to its
+// element.
+fq_status lower_projection_typed(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *values,
+                                 int32_t n_out, void *const *d_out, void *stream, bool need_data, const char *who,
+                                 ProjLaunch &P) {
+    if (n_out < 0 || n_out > FQ_MAX_PROJECT || (n_out > 0 && (!values || (need_data && !d_out))))
+        return fqc::fail(FQ_E_INVALID, std::string(who) + ": bad output list");
+    P = ProjLaunch{};
+    P.typed = true;
+    P.col = cols[0].data;
+    P.n = cols[0].len;
+    P.stream = (hipStream_t)stream;
+    P.n_cols = n_cols;
+    for (int j = 0; j < n_cols; ++j) {
+        P.cols[j] = cols[j].data;
+        P.cdt[j] = cols[j].dtype;
+    }
+    fq_status s = lower_pred_typed(pred, P.cdt, n_cols, P.n, need_data, P.pred);
+    if (s != FQ_OK) return s;
+    P.n_out = n_out;
+    for (int j = 0; j < n_out; ++j) {
+        if (need_data && !d_out[j] && P.n > 0) return fqc::fail(FQ_E_INVALID, std::string(who) + ": NULL output");
+        int32_t dt = P.cdt[0];
+        s = lower_expr_typed(values[j], P.cdt, n_cols, P.vals[j], dt);
+        if (s != FQ_OK) return s;
+        P.chain[j] = values[j].n_steps > 0;
+        P.dtypes[j] = dt;
+        P.out[j] = d_out ? d_out[j] : nullptr;
+        if (((uintptr_t)P.out[j]) % (uintptr_t)fqc::dtype_size(dt))
+            return fqc::fail(FQ_E_INVALID, std::string(who) + ": output not aligned to its element size");
+    }
+    set_typed_geometry(P);
+    return FQ_OK;
+}
+
 // fq_filter_project / fq_filter_project_columns after the lowering
 fq_status filter_project_run(int32_t col_dtype, const ProjLaunch &P, int64_t *out_len, void *d_ws, size_t ws_bytes) {
     fq_status s;
-    const std::string who = P.n_cols > 1 ? "fq_filter_project_columns" : "fq_filter_project";
+    const std::string who = P.typed ? "fq_filter_project_typed" : P.n_cols > 1 ? "fq_filter_project_columns" : "fq_filter_project";
     if (!jit_project_available())
         return fqc::fail(FQ_E_UNSUPPORTED, who + ": hipRTC unavailable or the JIT is off");
     if ((s = jit_project_prepare(col_dtype, P)) != FQ_OK) return s;
     const int64_t n = P.n;
     if (n == 0) return FQ_OK;
-    const ProjWs w = proj_ws(d_ws, n, P.n_cols);
+    const ProjWs w = proj_ws(d_ws, n, P.n_cols, project_tile_rows(P));
     const size_t need = (size_t)(2 + 16 + w.ntiles) * sizeof(uint64_t);
     if (!d_ws || ws_bytes < need) return fqc::fail(FQ_E_INVALID, who + ": workspace too small");
     hipStream_t st = P.stream;
@@ -613,13 +671,14 @@ fq_status filter_project_run(int32_t col_dtype, const ProjLaunch &P, int64_t *ou
 // fq_predicate_bitmap / fq_predicate_bitmap_columns after the lowering
 fq_status predicate_bitmap_run(int32_t col_dtype, ProjLaunch &P, uint64_t *d_bitmap, uint32_t *d_flag) {
     fq_status s;
-    const std::string who = P.n_cols > 1 ? "fq_predicate_bitmap_columns" : "fq_predicate_bitmap";
+    const std::string who = P.typed ? "fq_predicate_bitmap_typed" : P.n_cols > 1 ? "fq_predicate_bitmap_columns" : "fq_predicate_bitmap";
     if (P.pred.kind != FQ_PRED_EXPR && P.pred.kind != FQ_PRED_TREE)
         return fqc::fail(FQ_E_INVALID, who + ": needs an FQ_PRED_EXPR or FQ_PRED_TREE predicate");
     if (!jit_project_available())
         return fqc::fail(FQ_E_UNSUPPORTED, who + ": hipRTC unavailable or the JIT is off");
     P.n_out = 1;  // the module's shape needs one output; the bits kernel writes none
     P.dtypes[0] = col_dtype;
+    if (P.typed) set_typed_geometry(P);
     if ((s = jit_project_prepare(col_dtype, P)) != FQ_OK) return s;
     if (P.n == 0) return FQ_OK;
     if (!d_bitmap || !d_flag) return fqc::fail(FQ_E_INVALID, who + ": NULL buffer");
@@ -685,12 +744,14 @@ size_t fq_filter_project_blocks_workspace_bytes(void) { return 3 * sizeof(uint64
 
 namespace fqk {
 
-fq_status filter_project_blocks_enqueue_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows,
-                                                const fq_pred *pred, const fq_expr *values, int32_t n_out,
-                                                void *const *d_out, int64_t *d_counts, uint64_t *h_result,
-                                                uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
-                                                void *ev_end, void *stream) {
-    const std::string who = n_cols > 1 ? "fq_filter_project_blocks_columns" : "fq_filter_project_blocks";
+// typed: the call of fq_filter_project_blocks_typed with a narrow type in it (its columns checked)
+static fq_status blocks_enqueue(bool typed, const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                                const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                void *const *d_out, int64_t *d_counts, uint64_t *h_result,
+                                uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
+                                void *ev_end, void *stream) {
+    const std::string who = typed ? "fq_filter_project_blocks_typed"
+                                  : n_cols > 1 ? "fq_filter_project_blocks_columns" : "fq_filter_project_blocks";
     static_assert(FQ_PROJECT_MIN_BLOCK_ROWS == kProjectBlockTile, "the ABI's minimum block is the kernel's tile");
     if (!h_result) return fqc::fail(FQ_E_INVALID, who + ": NULL result words");
     // a resident call's words are the caller's until the hand-off writes them
@@ -700,7 +761,9 @@ fq_status filter_project_blocks_enqueue_columns(const fq_col *cols, int32_t n_co
         return fqc::fail(FQ_E_INVALID, who + ": block_rows below FQ_PROJECT_MIN_BLOCK_ROWS");
     ProjLaunch P;
     fq_status s;
-    if (n_cols == 1) {
+    if (typed) {
+        s = lower_projection_typed(cols, n_cols, pred, values, n_out, d_out, stream, true, who.c_str(), P);
+    } else if (n_cols == 1) {
         s = lower_projection(cols, pred, values, n_out, d_out, stream, P);
     } else {
         if ((s = check_cols(cols, n_cols, true, "fq_filter_project_blocks_columns")) != FQ_OK) return s;
@@ -751,12 +814,52 @@ fq_status filter_project_blocks_enqueue_columns(const fq_col *cols, int32_t n_co
     return FQ_OK;
 }
 
+fq_status filter_project_blocks_enqueue_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                                                const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                                void *const *d_out, int64_t *d_counts, uint64_t *h_result,
+                                                uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
+                                                void *ev_end, void *stream) {
+    return blocks_enqueue(false, cols, n_cols, block_rows, pred, values, n_out, d_out, d_counts, h_result, d_result, d_ws,
+                          ws_bytes, ev_start, ev_end, stream);
+}
+
+fq_status filter_project_blocks_enqueue_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows,
+                                              const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                              void *const *d_out, int64_t *d_counts, uint64_t *h_result,
+                                              uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
+                                              void *ev_end, void *stream) {
+    fq_status s = check_cols_typed(cols, n_cols, true, "fq_filter_project_blocks_typed");
+    if (s != FQ_OK) {
+        if (h_result && !d_result) h_result[0] = h_result[1] = 0;
+        return s;
+    }
+    const bool typed = !project_call_is_64(cols, n_cols, pred, values, n_out);
+    if (!typed && n_cols == 1 && (s = check_one_col_refs(cols, pred, values, n_out)) != FQ_OK) {
+        if (h_result && !d_result) h_result[0] = h_result[1] = 0;
+        return s;
+    }
+    return blocks_enqueue(typed, cols, n_cols, block_rows, pred, values, n_out, d_out, d_counts, h_result, d_result,
+                          d_ws, ws_bytes, ev_start, ev_end, stream);
+}
+
 fq_status filter_project_blocks_enqueue(const fq_col *col, int64_t block_rows, const fq_pred *pred,
                                         const fq_expr *values, int32_t n_out, void *const *d_out, int64_t *d_counts,
                                         uint64_t *h_result, uint64_t *d_result, void *d_ws, size_t ws_bytes,
                                         void *ev_start, void *ev_end, void *stream) {
     return filter_project_blocks_enqueue_columns(col, 1, block_rows, pred, values, n_out, d_out, d_counts, h_result,
                                                  d_result, d_ws, ws_bytes, ev_start, ev_end, stream);
+}
+
+bool typed_project_fits(const int32_t *cdt, int32_t n_cols, const fq_pred *pred, const fq_expr *values, int32_t n_out) {
+    if (!cdt || n_cols < 1 || n_cols > FQ_MAX_SCAN_COLS || n_out < 0 || n_out > FQ_MAX_PROJECT || (n_out > 0 && !values))
+        return false;
+    KProg val;
+    KPred kp;
+    for (int j = 0; j < n_out; ++j) {
+        int32_t dt = cdt[0];
+        if (lower_expr_typed(values[j], cdt, n_cols, val, dt) != FQ_OK) return false;
+    }
+    return lower_pred_typed(pred, cdt, n_cols, 0, false, kp) == FQ_OK;
 }
 
 fq_status filter_project_blocks_result(const uint64_t *h_result, int64_t *out_len) {
@@ -911,6 +1014,95 @@ fq_status fq_jit_prepare_project_columns(const fq_col *cols, int32_t n_cols, int
         s = lower_projection_cols(cols, n_cols, pred, values, n_out, nullptr, nullptr, false,
                                   "fq_jit_prepare_project_columns", P);
     }
+    if (s != FQ_OK) return s;
+    if (!jit_project_available()) return FQ_OK;  // the caller's unfused path answers
+    if ((s = jit_project_prepare(cols[0].dtype, P)) != FQ_OK) return s;
+    if (specialised) *specialised = 1;
+    return FQ_OK;
+}
+
+size_t fq_filter_project_typed_workspace_bytes(int64_t len, const fq_col *cols, int32_t n_cols) {
+    if (len < 0) len = 0;
+    // enough for the 64-bit twin and for the typed tile of these columns with an 8-byte output (the smallest)
+    size_t need = fq_filter_project_columns_workspace_bytes(len, n_cols);
+    if (cols && n_cols >= 1 && n_cols <= FQ_MAX_SCAN_COLS) {
+        int32_t cdt[FQ_MAX_SCAN_COLS];
+        for (int j = 0; j < n_cols; ++j) cdt[j] = fqc::dtype_is_numeric(cols[j].dtype) ? cols[j].dtype : FQ_DT_UINT64;
+        int rows = 0, group = 0;
+        fqk::typed_project_geometry(cdt, n_cols, 8, &rows, &group);
+        const fqk::ProjWs w = fqk::proj_ws(nullptr, len, n_cols, (int64_t)fqk::select_threads() * rows);
+        need = std::max(need, (size_t)(2 + 16 + w.ntiles) * sizeof(uint64_t));
+    }
+    return need;
+}
+
+fq_status fq_filter_project_typed(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *values,
+                                  int32_t n_out, void *const *d_out, int64_t *out_len, void *d_ws, size_t ws_bytes,
+                                  void *stream) {
+    using namespace fqk;
+    if (!out_len) return fqc::fail(FQ_E_INVALID, "fq_filter_project_typed: NULL out_len");
+    *out_len = 0;
+    fq_status s = check_cols_typed(cols, n_cols, true, "fq_filter_project_typed");
+    if (s != FQ_OK) return s;
+    if (project_call_is_64(cols, n_cols, pred, values, n_out))
+        return fq_filter_project_columns(cols, n_cols, pred, values, n_out, d_out, out_len, d_ws, ws_bytes, stream);
+    ProjLaunch P;
+    s = lower_projection_typed(cols, n_cols, pred, values, n_out, d_out, stream, true, "fq_filter_project_typed", P);
+    if (s != FQ_OK) return s;
+    if (n_out < 1) return fqc::fail(FQ_E_INVALID, "fq_filter_project_typed: no outputs");
+    return filter_project_run(cols[0].dtype, P, out_len, d_ws, ws_bytes);
+}
+
+fq_status fq_filter_project_blocks_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                         const fq_expr *values, int32_t n_out, void *const *d_out, int64_t *d_counts,
+                                         int64_t *out_len, void *d_ws, size_t ws_bytes, void *stream) {
+    using namespace fqk;
+    if (!out_len) return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks_typed: NULL out_len");
+    *out_len = 0;
+    fq_status s = check_cols_typed(cols, n_cols, true, "fq_filter_project_blocks_typed");
+    if (s != FQ_OK) return s;
+    if (project_call_is_64(cols, n_cols, pred, values, n_out))
+        return fq_filter_project_blocks_columns(cols, n_cols, block_rows, pred, values, n_out, d_out, d_counts, out_len,
+                                                d_ws, ws_bytes, stream);
+    uint64_t local[2] = {0, 0};
+    uint64_t *const pinned = fqc::host_staging();
+    uint64_t *const host = pinned ? pinned : local;  // kept rows, flag words
+    s = filter_project_blocks_enqueue_typed(cols, n_cols, block_rows, pred, values, n_out, d_out, d_counts, host, nullptr,
+                                            d_ws, ws_bytes, nullptr, nullptr, stream);
+    if (s != FQ_OK) return s;
+    FQ_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return filter_project_blocks_result(host, out_len);
+}
+
+fq_status fq_predicate_bitmap_typed(const fq_col *cols, int32_t n_cols, const fq_pred *pred, uint64_t *d_bitmap,
+                                    uint32_t *d_flag, void *stream) {
+    using namespace fqk;
+    fq_status s = check_cols_typed(cols, n_cols, true, "fq_predicate_bitmap_typed");
+    if (s != FQ_OK) return s;
+    if (call_is_64(cols, n_cols, pred, nullptr))
+        return fq_predicate_bitmap_columns(cols, n_cols, pred, d_bitmap, d_flag, stream);
+    ProjLaunch P;
+    s = lower_projection_typed(cols, n_cols, pred, nullptr, 0, nullptr, stream, true, "fq_predicate_bitmap_typed", P);
+    if (s != FQ_OK) return s;
+    return predicate_bitmap_run(cols[0].dtype, P, d_bitmap, d_flag);
+}
+
+fq_status fq_jit_prepare_project_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                       const fq_expr *values, int32_t n_out, int32_t *specialised) {
+    using namespace fqk;
+    if (specialised) *specialised = 0;
+    fq_status s = check_cols_typed(cols, n_cols, false, "fq_jit_prepare_project_typed");
+    if (s != FQ_OK) return s;
+    if (project_call_is_64(cols, n_cols, pred, values, n_out))
+        return fq_jit_prepare_project_columns(cols, n_cols, block_rows, pred, values, n_out, specialised);
+    if (block_rows != 0 && block_rows < FQ_PROJECT_MIN_BLOCK_ROWS)
+        return fqc::fail(FQ_E_INVALID, "fq_jit_prepare_project_typed: block_rows below FQ_PROJECT_MIN_BLOCK_ROWS");
+    if (n_out < 1 || n_out > FQ_MAX_PROJECT)
+        return fqc::fail(FQ_E_INVALID, "fq_jit_prepare_project_typed: n_out must be 1.." +
+                                           std::to_string(FQ_MAX_PROJECT) + ", got " + std::to_string(n_out));
+    ProjLaunch P;
+    s = lower_projection_typed(cols, n_cols, pred, values, n_out, nullptr, nullptr, false,
+                               "fq_jit_prepare_project_typed", P);
     if (s != FQ_OK) return s;
     if (!jit_project_available()) return FQ_OK;  // the caller's unfused path answers
     if ((s = jit_project_prepare(cols[0].dtype, P)) != FQ_OK) return s;

@@ -2932,7 +2932,46 @@ void pack_proj_consts(const ProjLaunch &P, HostProjConsts &hc) {
     pack_tree_consts(P.pred, hc);
 }
 
+// a typed module: the dtypes of columns, steps, comparisons and outputs, every
+// cast (a K_CAST step with both its types), every column reference, the load
+// geometry
+std::string typed_proj_shape_key(const ProjLaunch &P, int dev) {
+    std::string k = "PROJtyped";
+    auto put = [&k](int32_t v) { k.append(reinterpret_cast<const char *>(&v), sizeof v); };
+    put(dev);
+    put(P.n_cols);
+    for (int j = 0; j < P.n_cols; ++j) put(P.cdt[j]);
+    put(P.rows);
+    put(P.group);
+    put_pred_key(P.pred, k);
+    auto cols = [&put](const KProg &p) {
+        for (int i = 0; i < p.n; ++i) put(p.s[i].col);
+    };
+    put(P.pred.rhs_col);
+    cols(P.pred.lhs);
+    for (int l = 0; l < P.pred.n_leaves; ++l) {
+        put(P.pred.leaves[l].rhs_col);
+        cols(P.pred.leaves[l].lhs);
+    }
+    put(P.n_out);
+    for (int j = 0; j < P.n_out; ++j) {
+        put(P.dtypes[j]);
+        put(P.chain[j] ? P.vals[j].n : -1);
+        for (int i = 0; P.chain[j] && i < P.vals[j].n; ++i) {
+            const KStep &st = P.vals[j].s[i];
+            put(st.code);
+            put(st.operand);
+            put(st.reversed);
+            put(st.dtype);
+            put(st.sdtype);
+            put(st.col);
+        }
+    }
+    return k;
+}
+
 std::string proj_shape_key(const ProjLaunch &P, int32_t tin, int dev) {
+    if (P.typed) return typed_proj_shape_key(P, dev);
     // the tunable part of the shape: the block kernel's rows per thread and stage
     std::string k = "PROJb" + std::to_string(fqc::knob(FQ_TUNE_SELECT_BLOCKS_ROWS)) + "S" +
                     std::to_string(fqc::knob(FQ_TUNE_SELECT_BLOCKS_STAGE));
@@ -3426,8 +3465,8 @@ std::string gen_project_select_head_cols(int K) {
            "                                        " + FOR("const TIn@ (&x@)[PS_ROWS], ") + "u32 &pflags) {\n";
 }
 
-// ps_single, fq_jit_pselect and fq_jit_pmap
-std::string gen_project_select_tail_cols(int K) {
+// ps_single, fq_jit_pselect and (with_map) the 64-bit fq_jit_pmap
+std::string gen_project_select_tail_cols(int K, bool with_map = true) {
     auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
     const std::string XA = FOR("x@", ", ");
     const std::string U = std::to_string(std::max(1, 4 / K));  // 16-byte pairs per lane per column in flight (pmap)
@@ -3492,7 +3531,9 @@ fq_jit_pselect()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, Con
     if ((threadIdx.x & 63) == 0 && pflags) atomicOr(fl, pflags);
     if ((threadIdx.x & 63) == 0 && vflags) atomicOr(fl + 1, vflags);
 }
-
+)";
+    if (!with_map) return s;
+    s += R"(
 // every row: 16-byte loads and stores of row pairs when every column and every
 // output are 16-byte aligned (aligned != 0), else 8-byte rows
 extern "C" __global__ void __launch_bounds__(256)
@@ -3522,7 +3563,8 @@ fq_jit_pmap()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, Consts
     return s;
 }
 
-bool gen_project_source(const ProjLaunch &P, int32_t tin, int dev, Gen &g, std::string &src) {
+// The module's text up to its kernels: types, Consts, fq_pred, fq_val<j>, fq_put*.
+bool gen_project_head(const ProjLaunch &P, int32_t tin, Gen &g, std::string &src) {
     const char *TIn = ctype(tin);
     if (!TIn || P.n_out < 1 || P.n_out > FQ_MAX_PROJECT) return false;
     const int32_t pk = P.pred.kind;
@@ -3597,6 +3639,17 @@ __device__ __forceinline__ u32 wave_or(u32 f) {
     return f;
 }
 )";
+    return true;
+}
+
+bool gen_project_typed_head(const ProjLaunch &P, std::string &src);
+std::string gen_project_typed_kernels(const ProjLaunch &P);
+
+bool gen_project_source(const ProjLaunch &P, int32_t tin, int dev, Gen &g, std::string &src) {
+    // several columns, or a typed shape over one: the row is x0 .. x{K-1}
+    const int K = P.typed ? P.n_cols : (P.n_cols > 1 ? P.n_cols : 0);
+    auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    if (!(P.typed ? gen_project_typed_head(P, src) : gen_project_head(P, tin, g, src))) return false;
     if (K) src += gen_project_bits_cols(K);
     else src += R"(
 extern "C" __global__ void __launch_bounds__(256)
@@ -3811,8 +3864,8 @@ __device__ __forceinline__ bool ps_poll(const PsCtx &X, long long &j, u64 &excl,
 }
 )";
     if (K) {
-        src += gen_project_select_tail_cols(K);
-        src += gen_project_blocks_kernel(P, K);
+        src += gen_project_select_tail_cols(K, !P.typed);
+        src += P.typed ? gen_project_typed_kernels(P) : gen_project_blocks_kernel(P, K);
         return true;
     }
     src += R"(// one tile: draw, load, predicate, look back, store; false when none is left
@@ -3911,6 +3964,286 @@ fq_jit_pmap(const TIn *__restrict__ col, long long n, Consts c, Outs o, int alig
 )";
     src += gen_project_blocks_kernel(P, K);
     return true;
+}
+
+// ---------------------------------------------------------------------------
+// Typed Filter -> Projection (fq_filter_project_typed, _blocks_typed,
+// fq_predicate_bitmap_typed): columns, steps, comparisons and outputs of any
+// numeric type.  The module has the four kernels of the 64-bit one.  Its head
+// is kTypedCommon with fq_pred / fq_val<j> from the typed lowering
+// (emit_pred_typed / emit_prog_typed); fq_jit_pbits and fq_jit_pselect are the
+// several-columns text above over x0 .. x{K-1} in the columns' own types (one
+// row per lane per column, PS_ROWS = P.rows), every output stored at its own
+// width.  fq_jit_pmap and fq_jit_pblocks are below: a lane owns P.group
+// consecutive rows and loads its group * width bytes of each column as one
+// piece, as the typed scan does.
+// ---------------------------------------------------------------------------
+const char *piece_type(int bytes) { return bytes >= 16 ? "u32x4" : bytes == 8 ? "u64" : bytes == 4 ? "u32" : bytes == 2 ? "u16" : "u8"; }
+
+bool gen_project_typed_head(const ProjLaunch &P, std::string &src) {
+    const int K = P.n_cols;
+    if (K < 1 || K > FQ_MAX_SCAN_COLS || P.n_out < 1 || P.n_out > FQ_MAX_PROJECT) return false;
+    if (P.group < 1 || P.rows < P.group || P.rows % P.group || P.rows > 32) return false;
+    auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    TGen g;
+    for (int j = 0; j < K; ++j) {
+        if (!tname(P.cdt[j])) return false;
+        g.cdt[j] = P.cdt[j];
+    }
+    const std::string XP = FOR("TIn@ x@", ", "), XA = FOR("x@", ", ");
+    const bool expr_pred = P.pred.kind == FQ_PRED_EXPR || P.pred.kind == FQ_PRED_TREE;
+    std::string pred_body;
+    if (expr_pred && !emit_pred_typed(g, P.pred, pred_body)) return false;
+    src = kTypedCommon;
+    for (int j = 0; j < K; ++j) src += "typedef " + std::string(tname(P.cdt[j])) + " TIn" + std::to_string(j) + ";\n";
+    src += "struct Step { u64 c, m, s; };\nstruct Consts { u64 rhs; Step p[" + std::to_string(kSteps) + "], v[" +
+           std::to_string(FQ_MAX_PROJECT) + "][" + std::to_string(kSteps) + "]; u64 rl[" +
+           std::to_string(FQ_MAX_PRED_LEAVES) + "]; Step pl[" + std::to_string(FQ_MAX_PRED_LEAVES) + "][" +
+           std::to_string(kSteps) + "]; };\n";
+    src += "struct Outs { void *p[" + std::to_string(FQ_MAX_PROJECT) + "]; };\n";
+    src += "#define PS_ROWS " + std::to_string(P.rows) + "\n#define PS_THREADS " + std::to_string(select_threads()) +
+           "\n#define PS_SLEEP " + std::to_string(select_sleep()) + "\n";
+    src += "__device__ __forceinline__ bool fq_pred(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n";
+    src += expr_pred ? pred_body : std::string("    return true;\n");
+    src += "}\n";
+    std::string put_all = "__device__ __forceinline__ void fq_put(" + XP + ", const Consts &c, u32 &flags, u32 live, const Outs &o,\n"
+                          "                                       long long pos) {\n";
+    for (int j = 0; j < P.n_out; ++j) {
+        const char *V = tname(P.dtypes[j]);
+        if (!V) return false;
+        const std::string J = std::to_string(j);
+        std::string body;
+        TVal cur = g.X(0);  // n_steps == 0: the chain's start column as it is
+        if (P.chain[j] && !emit_prog_typed(g, body, P.vals[j], "v[" + J + "]", cur)) return false;
+        src += std::string("typedef ") + V + " V" + J + ";\n__device__ __forceinline__ V" + J + " fq_val" + J + "(" + XP +
+               ", const Consts &c, u32 &flags, u32 live) {\n" + body + "    return " + tcast(cur, P.dtypes[j]) + ";\n}\n";
+        put_all += "    ((V" + J + " *)o.p[" + J + "])[pos] = fq_val" + J + "(" + XA + ", c, flags, live);\n";
+    }
+    src += put_all + "}\n";
+    src += R"(
+__device__ __forceinline__ u32 wave_or(u32 f) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) f |= (u32)__shfl_xor((int)f, off, 64);
+    return f;
+}
+)";
+    return true;
+}
+
+// fq_jit_pmap and fq_jit_pblocks of a typed module.
+//
+// fq_jit_pmap (no predicate): with every column and output on the group's grid
+// (aligned != 0) a lane loads PM_U groups' pieces, evaluates every output for
+// its rows and stores each output's group as one piece; the rows past the last
+// whole group, and every row otherwise, go one row per lane.
+//
+// fq_jit_pblocks: fq_jit_pblocks' walk (one block per draw from the counter,
+// tiles of 256 * PB_ROWS rows, a block's kept rows at its running count) with a
+// tile's rows held as PB_NS slabs of 256 * PB_G rows: lane l of slab k owns rows
+// (256 k + l) PB_G + [0, PB_G).  A group on the grid of every column (its first
+// row a multiple of PB_G elements from a PB_G * width boundary) and wholly
+// inside the block is loaded as pieces; any other group -- the block's ragged
+// end, columns out of phase, a block that starts off the grid -- element by
+// element into the same registers, so row i of one column always meets row i
+// of the others.  In-tile ranks: a lane's kept count per slab, an inclusive
+// scan over the wave (two slabs' counts share one 32-bit word), the waves'
+// totals scanned through LDS; a kept row's rank is its slab-and-wave offset
+// plus the lanes below it plus the lane's own earlier kept rows.  Outputs as
+// the several-columns kernel writes them, at the output's width: each lane
+// evaluates output j for its kept rows from registers and writes it to the LDS
+// stage by rank; after a barrier consecutive threads store the run.  The stage
+// slot of rank 0 lies as far into a 16-byte line as its destination, so the
+// part of the run between 16-byte boundaries goes out as 16-byte non-temporal
+// stores whatever the output's alignment, its ragged head and tail as elements.
+std::string gen_project_typed_kernels(const ProjLaunch &P) {
+    const int K = P.n_cols, G = P.group, NS = P.rows / P.group;
+    auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    int sum = 0, wout = 1;
+    std::string s = "#define PB_G " + std::to_string(G) + "\n";
+    for (int j = 0; j < K; ++j) {
+        const int B = G * fqc::dtype_size(P.cdt[j]);
+        sum += fqc::dtype_size(P.cdt[j]);
+        s += "typedef " + std::string(piece_type(B)) + " P" + std::to_string(j) + ";\n#define NP" + std::to_string(j) + " " +
+             std::to_string(B >= 16 ? B / 16 : 1) + "\n";
+    }
+    for (int j = 0; j < P.n_out; ++j) {
+        const int B = G * fqc::dtype_size(P.dtypes[j]);
+        wout = std::max(wout, fqc::dtype_size(P.dtypes[j]));
+        s += "typedef " + std::string(piece_type(B)) + " PO" + std::to_string(j) + ";\n#define NPO" + std::to_string(j) + " " +
+             std::to_string(B >= 16 ? B / 16 : 1) + "\n";
+    }
+    // the lane's rows of group `raw` as typed elements y@[PB_G]
+    auto ROWS = [&FOR](const std::string &ind, const std::string &raw) {
+        return FOR(ind + "TIn@ y@[PB_G];\n" + ind + "__builtin_memcpy(&y@[0], &" + raw + "[0], PB_G * sizeof(TIn@));\n");
+    };
+    s += "#define PM_U " + std::to_string(std::max(1, 128 / (G * sum))) + "\n";
+    s += "extern \"C\" __global__ void __launch_bounds__(256)\nfq_jit_pmap(" + FOR("const TIn@ *__restrict__ col@, ") +
+         "long long n, Consts c, Outs o, int aligned, u32 *__restrict__ fl) {\n"
+         "    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;\n"
+         "    const long long T = (long long)gridDim.x * 256;\n"
+         "    u32 flags = 0;\n"
+         "    long long done = 0;\n"
+         "    if (aligned) {\n"
+         "        const long long ngrp = n / PB_G;\n" +
+         FOR("        const P@ *__restrict__ pp@ = (const P@ *)col@;\n") +
+         "        for (long long g0 = g; g0 < ngrp; g0 += PM_U * T) {\n" + FOR("            P@ raw@[PM_U][NP@];\n") +
+         "#pragma unroll\n            for (int u = 0; u < PM_U; ++u) {\n"
+         "                const long long gi = g0 + (long long)u * T;\n"
+         "                if (gi < ngrp) {\n" +
+         FOR("                    _Pragma(\"unroll\") for (int q = 0; q < NP@; ++q) raw@[u][q] = "
+             "__builtin_nontemporal_load(pp@ + gi * NP@ + q);\n") +
+         "                }\n            }\n"
+         "#pragma unroll\n            for (int u = 0; u < PM_U; ++u) {\n"
+         "                const long long gi = g0 + (long long)u * T;\n"
+         "                if (gi < ngrp) {\n" + ROWS("                    ", "raw@[u]");
+    for (int j = 0; j < P.n_out; ++j) {
+        const std::string J = std::to_string(j);
+        s += "                    {\n                        V" + J + " v[PB_G];\n"
+             "                        _Pragma(\"unroll\") for (int r = 0; r < PB_G; ++r) v[r] = fq_val" + J + "(" +
+             FOR("y@[r]", ", ") + ", c, flags, 1u);\n"
+             "                        PO" + J + " ov[NPO" + J + "];\n"
+             "                        __builtin_memcpy(&ov[0], &v[0], sizeof(ov));\n"
+             "                        _Pragma(\"unroll\") for (int q = 0; q < NPO" + J + "; ++q) __builtin_nontemporal_store(ov[q], ((PO" + J +
+             " *)o.p[" + J + "]) + gi * NPO" + J + " + q);\n                    }\n";
+    }
+    s += "                }\n            }\n        }\n        done = ngrp * PB_G;\n    }\n"
+         "    for (long long i = done + g; i < n; i += T) fq_put(" + FOR("col@[i]", ", ") + ", c, flags, 1u, o, i);\n"
+         "    flags = wave_or(flags);\n"
+         "    if ((threadIdx.x & 63) == 0 && flags) atomicOr(fl, flags);\n}\n";
+
+    s += "#define PB_ROWS " + std::to_string(P.rows) + "\n#define PB_WOUT " + std::to_string(wout) + "\n";
+    s += R"(#define PB_THREADS 256
+#define PB_WAVES (PB_THREADS / 64)
+#define PB_TILE (PB_THREADS * PB_ROWS)
+#define PB_NS (PB_ROWS / PB_G)     // slabs of PB_THREADS * PB_G rows per tile
+#define PB_NE (PB_NS * PB_WAVES)   // (slab, wave) runs of 64 * PB_G rows per tile, in row order
+typedef u32x4 u32x4a __attribute__((may_alias));
+// exclusive scan of the PB_NE (<= 32) run counts in off[] by wave 0; off[PB_NE] = the tile's kept rows
+__device__ __forceinline__ void pb_scan(u32 *__restrict__ off, int lane) {
+    const u32 v = lane < PB_NE ? off[lane] : 0u;
+    u32 incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u32 t = (u32)__shfl_up((int)incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    if (lane < PB_NE) off[lane] = incl - v;
+    if (lane == 63) off[PB_NE] = incl;
+}
+// ranks [0, tot) of the staged output, rank r in st[r], go to dst[r]; st is as
+// far into a 16-byte line of the stage as dst into one of the output
+template <typename V>
+__device__ __forceinline__ void pb_copy(const V *__restrict__ st, u32 tot, V *__restrict__ dst, int tid) {
+    constexpr u32 E = 16 / sizeof(V);
+    const u32 mis = (u32)(((unsigned long long)dst & 15ull) / sizeof(V));
+    u32 h = mis ? E - mis : 0u;  // elements before the first 16-byte boundary
+    if (h > tot) h = tot;
+    const u32 nv = (tot - h) / E, t0 = h + nv * E;
+    if ((u32)tid < h) __builtin_nontemporal_store(st[tid], dst + tid);
+    if (tid >= 64 && (u32)tid - 64u < tot - t0) __builtin_nontemporal_store(st[t0 + tid - 64], dst + t0 + tid - 64);
+    const u32x4a *__restrict__ sv = (const u32x4a *)(st + h);
+    u32x4 *__restrict__ dv = (u32x4 *)(dst + h);
+    for (u32 q = tid; q < nv; q += PB_THREADS) {
+        const u32x4 v = sv[q];
+        __builtin_nontemporal_store(v, dv + q);
+    }
+}
+extern "C" __global__ void __launch_bounds__(PB_THREADS)
+fq_jit_pblocks()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, long long B, Consts c,
+    const u64 *__restrict__ bm, Outs o, long long *__restrict__ counts, u32 *__restrict__ fl,
+    unsigned long long *__restrict__ total, u32 *__restrict__ ticket, int al) {
+    (void)al;
+    __shared__ u32 off[PB_NE + 1];
+    __shared__ u32x4 stage[(PB_TILE * PB_WOUT) / 16 + 2];
+    __shared__ long long s_run;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long nb = (n + B - 1) / B;
+    u64 kept = 0;  // the workgroup's kept rows
+    u32 pflags = 0, vflags = 0;
+    // one block per draw from the counter: the blocks in flight stay adjacent
+    for (;;) {
+        if (tid == 0) s_run = (long long)atomicAdd(ticket, 1u);
+        __syncthreads();
+        const long long run = s_run;
+        if (run >= nb) break;
+        const long long end = (run + 1) * B < n ? (run + 1) * B : n;
+        u64 carry = 0;  // the block's kept rows so far
+        for (long long r0 = run * B; r0 < end; r0 += PB_TILE) {
+)" + FOR("            P@ raw@[PB_NS][NP@];\n") +
+         "            const bool grid = ((" + FOR("(unsigned long long)(col@ + r0) & (PB_G * sizeof(TIn@) - 1)", " | ") +
+         ") == 0ull);\n"
+         "#pragma unroll\n            for (int k = 0; k < PB_NS; ++k) {\n"
+         "                const long long row = r0 + (long long)(k * PB_THREADS + tid) * PB_G;\n"
+         "                if (grid && row + PB_G <= end) {\n" +
+         FOR("                    _Pragma(\"unroll\") for (int q = 0; q < NP@; ++q) raw@[k][q] = "
+             "__builtin_nontemporal_load((const P@ *)(col@ + row) + q);\n") +
+         "                } else {\n" +
+         FOR("                    TIn@ y@[PB_G];\n"
+             "                    _Pragma(\"unroll\") for (int r = 0; r < PB_G; ++r) y@[r] = row + r < end ? "
+             "__builtin_nontemporal_load(col@ + row + r) : TIn@(0);\n"
+             "                    __builtin_memcpy(&raw@[k][0], &y@[0], PB_G * sizeof(TIn@));\n") +
+         "                }\n            }\n"
+         "            u32 m[PB_NS], rk[PB_NS];  // the lane's kept rows of each slab; the rank of the first of them\n"
+         "#pragma unroll\n            for (int k = 0; k < PB_NS; ++k) {\n"
+         "                const long long row = r0 + (long long)(k * PB_THREADS + tid) * PB_G;\n" +
+         ROWS("                ", "raw@[k]") +
+         "                u32 mk = 0;\n"
+         "#pragma unroll\n                for (int r = 0; r < PB_G; ++r) {\n"
+         "                    const u32 live = row + r < end ? 1u : 0u;\n";
+    s += P.pred.kind == FQ_PRED_BITMAP
+             ? std::string("                    const bool p = live && ((bm[(row + r) >> 6] >> ((row + r) & 63)) & 1ull);\n"
+                           "                    (void)c;\n")
+             : "                    const bool p = fq_pred(" + FOR("y@[r]", ", ") + ", c, pflags, live) && live;\n";
+    s += "                    mk |= p ? (1u << r) : 0u;\n                }\n                m[k] = mk;\n            }\n";
+    for (int k = 0; k < NS; k += 2) {
+        const std::string A = std::to_string(k), Bk = std::to_string(k + 1);
+        const bool two = k + 1 < NS;
+        s += "            {\n                const u32 v = (u32)__popc(m[" + A + "])" +
+             (two ? " | ((u32)__popc(m[" + Bk + "]) << 16)" : std::string()) + ";\n"
+             "                u32 incl = v;\n"
+             "#pragma unroll\n                for (int d = 1; d < 64; d <<= 1) {\n"
+             "                    const u32 t = (u32)__shfl_up((int)incl, d, 64);\n"
+             "                    if (lane >= d) incl += t;\n                }\n"
+             "                rk[" + A + "] = (incl - v) & 0xffffu;\n" +
+             (two ? "                rk[" + Bk + "] = (incl - v) >> 16;\n" : std::string()) +
+             "                if (lane == 63) {\n                    off[" + A + " * PB_WAVES + wave] = incl & 0xffffu;\n" +
+             (two ? "                    off[" + Bk + " * PB_WAVES + wave] = incl >> 16;\n" : std::string()) +
+             "                }\n            }\n";
+    }
+    s += R"(            __syncthreads();
+            if (wave == 0) pb_scan(off, lane);
+            __syncthreads();
+            const u32 tot = off[PB_NE];
+#pragma unroll
+            for (int k = 0; k < PB_NS; ++k) rk[k] += off[k * PB_WAVES + wave];
+            const long long base = run * B + (long long)carry;
+)";
+    for (int j = 0; j < P.n_out; ++j) {
+        const std::string J = std::to_string(j);
+        s += "            {\n                V" + J + " *__restrict__ dst = (V" + J + " *)o.p[" + J + "] + base;\n"
+             "                V" + J + " *__restrict__ st = (V" + J + " *)stage + (u32)(((unsigned long long)dst & 15ull) / sizeof(V" + J + "));\n" +
+             (j ? "                __syncthreads();  // the stage is read out\n" : "") +
+             "#pragma unroll\n                for (int k = 0; k < PB_NS; ++k) {\n" + ROWS("                    ", "raw@[k]") +
+             "#pragma unroll\n                    for (int r = 0; r < PB_G; ++r)\n"
+             "                        if ((m[k] >> r) & 1u)\n"
+             "                            st[rk[k] + (u32)__popc(m[k] & ((1u << r) - 1u))] = fq_val" + J + "(" + FOR("y@[r]", ", ") +
+             ", c, vflags, 1u);\n                }\n"
+             "                __syncthreads();\n"
+             "                pb_copy<V" + J + ">(st, tot, dst, tid);\n            }\n";
+    }
+    s += R"PB(            carry += tot;
+        }
+        if (tid == 0) counts[run] = (long long)carry;
+        kept += carry;
+    }
+    pflags = wave_or(pflags);
+    vflags = wave_or(vflags);
+    if (lane == 0 && pflags) atomicOr(fl, pflags);
+    if (lane == 0 && vflags) atomicOr(fl + 1, vflags);
+    if (tid == 0 && kept) atomicAdd(total, (unsigned long long)kept);
+}
+)PB";
+    return s;
 }
 
 // ---------------------------------------------------------------------------
@@ -4340,7 +4673,7 @@ fq_status jit_project_select(int32_t col_dtype, const ProjLaunch &P, const uint6
     } outs;
     for (int j = 0; j < FQ_MAX_PROJECT; ++j) outs.p[j] = j < P.n_out ? P.out[j] : nullptr;
     long long n = P.n;
-    const int64_t ntiles = (P.n + select_tile_rows(P.n_cols) - 1) / select_tile_rows(P.n_cols);
+    const int64_t ntiles = (P.n + project_tile_rows(P) - 1) / project_tile_rows(P);
     ProjArgs pa(P);
     void **args = pa.with(&n, &hc, &d_bitmap, &outs, &status, &ticket, &d_flags, &d_total);
     const int wg_per_cu = (int)fqc::knob(FQ_TUNE_SELECT_WG_PER_CU);
@@ -4439,9 +4772,26 @@ fq_status jit_project_map(int32_t col_dtype, const ProjLaunch &P, uint32_t *d_fl
         if (j < P.n_out && ((uintptr_t)P.out[j] & 15u)) aligned = 0;
     }
     long long n = P.n;
+    int64_t units = n / 2;  // row pairs, four per lane in flight
+    int per_wg = kThreads * 4;
+    if (P.typed) {
+        // every column and output on the group's grid: pieces of group * width bytes (16-byte vectors from 16 up)
+        auto on_grid = [&P](const void *p, int32_t dt) {
+            return ((uintptr_t)p % (uintptr_t)(P.group * fqc::dtype_size(dt))) == 0;
+        };
+        aligned = 1;
+        int sum = 0;
+        for (int j = 0; j < P.n_cols; ++j) {
+            aligned &= on_grid(P.n_cols > 1 ? P.cols[j] : P.col, P.cdt[j]) ? 1 : 0;
+            sum += fqc::dtype_size(P.cdt[j]);
+        }
+        for (int j = 0; j < P.n_out; ++j) aligned &= on_grid(P.out[j], P.dtypes[j]) ? 1 : 0;
+        units = n / P.group;  // groups, PM_U per lane in flight (gen_project_typed_kernels)
+        per_wg = kThreads * std::max(1, 128 / (P.group * sum));
+    }
     ProjArgs pa(P);
     void **args = pa.with(&n, &hc, &outs, &aligned, &d_flag);
-    FQ_HIP_TRY(hipModuleLaunchKernel(k.map, (unsigned)proj_grid(n / 2, kThreads * 4), 1, 1, kThreads, 1, 1, 0, P.stream,
+    FQ_HIP_TRY(hipModuleLaunchKernel(k.map, (unsigned)proj_grid(units, per_wg), 1, 1, kThreads, 1, 1, 0, P.stream,
                                      args, nullptr));
     g_jit_launches += 1;
     return FQ_OK;

@@ -95,6 +95,11 @@ fq_status lower_pred_typed(const fq_pred *pred, const int32_t *cdt, int n_cols, 
 // Argument checks of the *_columns entry points: 1..FQ_MAX_SCAN_COLS columns of
 // equal len, each UINT64 / INT64 / FLOAT64 (`who` names the caller in the messages).
 fq_status check_cols(const fq_col *cols, int32_t n_cols, bool need_data, const char *who = "fq_aggregate_columns");
+// The same for the *_typed entry points (any numeric dtype each), and whether
+// every column, step and comparison type of a call is 64-bit (the call then IS
+// its *_columns twin).
+fq_status check_cols_typed(const fq_col *cols, int32_t n_cols, bool need_data, const char *who);
+bool call_is_64(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *value);
 
 // Flat scan over K >= 2 columns: 16-byte vectors per lane per column in a
 // tile, the next tile's as many in flight.  One column holds 2 x 4; K columns
@@ -226,7 +231,36 @@ struct ProjLaunch {
     int n_cols;
     const void *cols[FQ_MAX_SCAN_COLS];
     int32_t cdt[FQ_MAX_SCAN_COLS];
+    // the *_typed entry points with a narrow column, step, comparison or output
+    // (n_cols >= 1): `rows` per thread per tile of 256 * rows rows; in the
+    // block-stream and map kernels a lane owns `group` consecutive rows and
+    // loads its group * width bytes of every column in one piece
+    // (typed_project_geometry)
+    bool typed;
+    int rows;
+    int group;
 };
+
+// Load geometry of a typed projection over columns of widths cdt whose widest
+// output has wout bytes.  Rows per thread per tile R: the largest power of two
+// <= 32 with R * sum(w) <= 384 bytes of row data per lane (the measured K = 3
+// point of project_cols_rows: 16 rows of three 8-byte columns) and R * wout <=
+// 128, so that the LDS stage of one output of one tile stays within the 32 KB
+// the 64-bit kernels use; the tile of 256 * R rows never exceeds
+// FQ_PROJECT_MIN_BLOCK_ROWS.  Row group G: the largest power of two <= 16 and
+// <= R with G * sum(w) <= 128 bytes (typed_group's bound without a prefetch:
+// the tile's other groups are the loads in flight); G >= 4, so every piece is a
+// 4- or 8-byte word or whole 16-byte vectors.
+inline void typed_project_geometry(const int32_t *cdt, int n_cols, int wout, int *rows, int *group) {
+    int sum = 0;
+    for (int j = 0; j < n_cols; ++j) sum += fqc::dtype_size(cdt[j]);
+    int r = 32;
+    while (r > 1 && (r * sum > 384 || r * wout > 128)) r >>= 1;
+    int g = 16;
+    while (g > 1 && (g > r || g * sum > 128)) g >>= 1;
+    *rows = r;
+    *group = g;
+}
 
 // Rows per thread per tile of the look-back and block-stream kernels over K
 // columns: 16, 16, 8 for K = 2, 3, 4 (64, 96, 64 VGPRs of row data; one column
@@ -251,6 +285,10 @@ constexpr int select_threads() { return 256; }
 constexpr int select_rows_per_thread() { return 32; }
 constexpr int select_sleep() { return 2; }
 constexpr int64_t select_tile_rows(int n_cols = 1) { return (int64_t)select_threads() * project_cols_rows(n_cols); }
+// the look-back tile of P: a typed call's 256 * rows
+inline int64_t project_tile_rows(const ProjLaunch &P) {
+    return P.typed ? (int64_t)select_threads() * P.rows : select_tile_rows(P.n_cols);
+}
 fq_status jit_project_select(int32_t col_dtype, const ProjLaunch &P, const uint64_t *d_bitmap, uint64_t *status,
                              uint32_t *ticket, uint32_t *d_flags, uint64_t *d_total);
 // stream of DataBlocks of block_rows rows (fq_filter_project_blocks): block b's

@@ -26,6 +26,8 @@ GPU_SYMBOLS = [
     "fq_blocks_compact_workspace_bytes", "fq_blocks_compact", "fq_aggregate_columns", "fq_jit_prepare_columns",
     "fq_filter_project_columns_workspace_bytes", "fq_filter_project_columns", "fq_filter_project_blocks_columns",
     "fq_predicate_bitmap_columns", "fq_jit_prepare_project_columns", "fq_aggregate_typed", "fq_jit_prepare_typed",
+    "fq_filter_project_typed_workspace_bytes", "fq_filter_project_typed", "fq_filter_project_blocks_typed",
+    "fq_predicate_bitmap_typed", "fq_jit_prepare_project_typed",
 ]
 
 
@@ -106,6 +108,15 @@ _protos = {
     "fq_predicate_bitmap_columns": (C.c_int32, [P(abi.fq_col), C.c_int32, P(abi.fq_pred), vp, vp, vp]),
     "fq_jit_prepare_project_columns": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred),
                                                    P(abi.fq_expr), C.c_int32, P(C.c_int32)]),
+    "fq_filter_project_typed_workspace_bytes": (C.c_size_t, [C.c_int64, P(abi.fq_col), C.c_int32]),
+    "fq_filter_project_typed": (C.c_int32, [P(abi.fq_col), C.c_int32, P(abi.fq_pred), P(abi.fq_expr), C.c_int32,
+                                            P(vp), P(C.c_int64), vp, C.c_size_t, vp]),
+    "fq_filter_project_blocks_typed": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred),
+                                                   P(abi.fq_expr), C.c_int32, P(vp), vp, P(C.c_int64), vp,
+                                                   C.c_size_t, vp]),
+    "fq_predicate_bitmap_typed": (C.c_int32, [P(abi.fq_col), C.c_int32, P(abi.fq_pred), vp, vp, vp]),
+    "fq_jit_prepare_project_typed": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred),
+                                                 P(abi.fq_expr), C.c_int32, P(C.c_int32)]),
     "fq_group_table_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "fq_group_table_init": (C.c_int32, [P(abi.fq_group_table), vp]),
     "fq_group_aggregate": (C.c_int32, [P(abi.fq_group_table), P(abi.fq_col), P(abi.fq_pred), P(abi.fq_expr),

@@ -34,7 +34,7 @@ DT_BY_NAME = {v: k for k, v in DT_NAMES.items()}
 OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MOD = 0, 1, 2, 3, 4
 OP_PUSH = 5  # expression trees: push acc, acc = the column
 OP_LOAD = 6  # fq_aggregate_columns: acc = column `bits` (first step only)
-MAX_SCAN_COLS = 4  # columns of one fq_aggregate_columns / fq_aggregate_typed scan / fq_filter_project_columns call
+MAX_SCAN_COLS = 4  # columns of one fq_aggregate_columns / fq_aggregate_typed scan / fq_filter_project_columns / _typed call
 MAX_PROJECT = 8  # outputs of one fused projection
 PROJECT_MIN_BLOCK_ROWS = 8192
 OP_BY_SYM = {"+": OP_ADD, "-": OP_SUB, "*": OP_MUL, "/": OP_DIV, "%": OP_MOD}

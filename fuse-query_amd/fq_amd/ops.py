@@ -470,6 +470,86 @@ def jit_prepare_project_columns(dtypes, pred=None, values=(None,), block_rows=0,
     return bool(out.value)
 
 
+# ---- the same over columns, steps, comparisons and outputs of any numeric type ----
+def filter_project_typed(cols, pred, values, stream=None, out_offset=0):
+    """fq_filter_project_typed over a list of DeviceColumns of any numeric
+    dtype each: the kept rows (pred None = all) through each fq_expr of
+    `values` (None = column 0 itself) -> [DeviceColumn], each of its
+    expression's out_dtype at that type's own width.  out_offset: each output a
+    view that many of its elements into its buffer."""
+    require_gpu()
+    n_out, n = len(values), cols[0].len
+    exprs = _project_exprs(values, cols[0].dtype)
+    outs = []
+    for j in range(n_out):
+        dt = exprs[j].out_dtype
+        full = empty_column(n + out_offset, dt)
+        outs.append(DeviceColumn(full.buf, n, dt, offset=ELEM_SIZE[dt] * out_offset) if out_offset else full)
+    ptrs = (C.c_void_p * max(n_out, 1))(*[o.ptr for o in outs])
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    ws = Workspace(lib.fq_filter_project_typed_workspace_bytes(n, arr, len(cols)))
+    kept = C.c_int64(0)
+    check(lib.fq_filter_project_typed(arr, len(cols), C.byref(pred) if pred is not None else None, exprs, n_out,
+                                      ptrs, C.byref(kept), ws.ptr, ws.nbytes, _stream(stream)))
+    for o in outs:
+        o.len = kept.value
+    return outs
+
+
+def filter_project_blocks_typed(cols, block_rows, pred, values, stream=None, out_offset=0, fill=None):
+    """fq_filter_project_blocks_typed: filter_project_blocks_columns over
+    DeviceColumns of any numeric dtype -> ([DeviceColumn of len rows per
+    output, in its out_dtype], per-block kept counts, rows kept).  out_offset:
+    each output a view that many of its elements into its buffer; fill: a byte
+    value the output buffers are set to first (rows past a block's count must
+    be left as they were)."""
+    require_gpu()
+    n_out, n = len(values), cols[0].len
+    exprs = _project_exprs(values, cols[0].dtype)
+    outs = []
+    for j in range(n_out):
+        dt = exprs[j].out_dtype
+        full = empty_column(n + out_offset, dt)
+        if fill is not None:
+            full.buf.fill_(int(fill) & 0xFF)
+        outs.append(DeviceColumn(full.buf, n, dt, offset=ELEM_SIZE[dt] * out_offset) if out_offset else full)
+    ptrs = (C.c_void_p * max(n_out, 1))(*[o.ptr for o in outs])
+    nb = (1 if block_rows >= n else -(-n // block_rows)) if block_rows > 0 and n > 0 else 0
+    counts = Workspace(max(8 * nb, 8))
+    ws = Workspace(lib.fq_filter_project_blocks_workspace_bytes())
+    kept = C.c_int64(0)
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    check(lib.fq_filter_project_blocks_typed(arr, len(cols), block_rows, C.byref(pred) if pred is not None else None,
+                                             exprs, n_out, ptrs, counts.ptr, C.byref(kept), ws.ptr, ws.nbytes,
+                                             _stream(stream)))
+    cnt = counts.buf[:8 * nb].view(torch.int64).cpu().numpy() if nb else np.zeros(0, np.int64)
+    return outs, cnt, kept.value
+
+
+def predicate_bitmap_typed(cols, pred, stream=None):
+    """fq_predicate_bitmap_typed: the predicate over DeviceColumns of any
+    numeric dtype as a Boolean column."""
+    require_gpu()
+    out = empty_column(cols[0].len, abi.DT_BOOLEAN)
+    flag = Workspace(4)
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    check(lib.fq_predicate_bitmap_typed(arr, len(cols), C.byref(pred), C.c_void_p(out.ptr), flag.ptr, _stream(stream)))
+    return out
+
+
+def jit_prepare_project_typed(dtypes, pred=None, values=(None,), block_rows=0, length=1 << 30, lengths=None):
+    """jit_prepare_project_columns for the *_typed entry points: one dtype (any
+    numeric) per column; works without a GPU."""
+    lens = list(lengths) if lengths is not None else [int(length)] * len(dtypes)
+    arr = (abi.fq_col * max(len(dtypes), 1))(*[abi.fq_col(None, int(n), dt, 0) for dt, n in zip(dtypes, lens)])
+    exprs = _project_exprs(values, dtypes[0] if dtypes else 0)
+    out = C.c_int32(0)
+    check(lib.fq_jit_prepare_project_typed(arr, len(dtypes), int(block_rows),
+                                           C.byref(pred) if pred is not None else None, exprs, len(values),
+                                           C.byref(out)))
+    return bool(out.value)
+
+
 def project_compile_check(col_dtype, pred=None, values=(None,)):
     """Generate + compile the fused projection module for this shape without
     running it (no GPU needed: gfx950 code object only).  Returns the

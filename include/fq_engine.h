@@ -322,8 +322,9 @@ fq_status fq_functions_accumulate(fq_engine *e, fq_function *const *fs, int32_t 
  * func.eval(&block)?.to_array(block.num_rows()) }`) over n handles at once,
  * honouring the block's pending `filter` and its `block_rows`.  d_out: n
  * caller-owned device buffers of `cap` bytes each.  out_dtypes[i]: the dtype
- * of output i; *out_len: the rows every output holds; *out_bytes: the bytes an
- * output needs (FQ_E_INVALID when cap is short).
+ * of output i, each output written at that type's own width; *out_len: the
+ * rows every output holds; *out_bytes: the bytes an output needs, the widest
+ * output's (FQ_E_INVALID when cap is short).
  *   d_counts == NULL  each output holds the kept rows concatenated, as n
  *                     fq_function_eval calls would leave them;
  *   d_counts != NULL  block-stream geometry (fq_filter_project_blocks): block
@@ -331,10 +332,12 @@ fq_status fq_functions_accumulate(fq_engine *e, fq_function *const *fs, int32_t 
  *                     output (device int64 per block), *out_len the rows kept
  *                     over all blocks; needs block_rows >=
  *                     FQ_PROJECT_MIN_BLOCK_ROWS and cap >= 8 x the block's
- *                     rows (FQ_E_INVALID), 64-bit outputs only.
+ *                     rows (FQ_E_INVALID), numeric outputs only.
  * When the filter and every function are expressions over up to
- * FQ_MAX_SCAN_COLS 64-bit columns (at most FQ_MAX_PROJECT functions, the JIT
- * on), ONE fused kernel serves the whole call -- no compacted copy of the
+ * FQ_MAX_SCAN_COLS numeric columns (at most FQ_MAX_PROJECT functions with
+ * numeric results, the JIT on; a narrow column, step, comparison or output
+ * sends the block to the fq_filter_project*_typed kernels), ONE fused kernel
+ * serves the whole call -- no compacted copy of the
  * block, no array per expression node -- and *fused = 1; the contiguous form
  * writes straight into d_out when cap >= 8 x the block's rows.  Otherwise
  * *fused = 0: either the functions fuse but the filter does not (or its

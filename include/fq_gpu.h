@@ -434,6 +434,49 @@ fq_status fq_predicate_bitmap_columns(const fq_col *cols, int32_t n_cols, const 
 fq_status fq_jit_prepare_project_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
                                          const fq_expr *values, int32_t n_out, int32_t *specialised);
 
+/* ---- Filter -> Projection over columns, steps, comparisons and outputs of any numeric type ----
+ * (`SELECT price * discount, quantity WHERE shipdate < k and quantity < q` over
+ * price Float64, discount Float32, shipdate Int32, quantity UInt8).  The twins
+ * of the four *_columns entry points above: cols[0..n_cols) have equal len and
+ * any numeric dtype each, 1..FQ_MAX_SCAN_COLS of them, with the column
+ * references of fq_aggregate_columns.  Every fq_step.dtype, cmp_dtype and
+ * out_dtype may be any numeric type and is checked against numerical_coercion
+ * / equal_coercion of its operands exactly as fq_aggregate_typed checks them
+ * (FQ_E_INVALID; "expression too long" when the inserted casts exceed the
+ * program); casts, wrapping + - *, truncating / %, Float32 steps and zero
+ * divisors follow the rules documented at fq_aggregate_typed.
+ *
+ * d_out[j] holds elements of values[j].out_dtype at that type's own width (1,
+ * 2, 4 or 8 bytes) and is aligned to it; values[j].n_steps == 0 writes column
+ * 0 as it is (a lone FQ_OP_LOAD step: that column).  The block-stream form
+ * keeps fq_filter_project_blocks' geometry in rows: block b's kept rows at rows
+ * [b * block_rows, b * block_rows + d_counts[b]) of each output, rows past the
+ * count untouched, block_rows >= FQ_PROJECT_MIN_BLOCK_ROWS.  The error order,
+ * predicate kinds, *out_len and the synchronisation are the *_columns entry
+ * points'; a cast that arrow turns into null on a row that reaches it (any row
+ * for the predicate, a kept row for a value) is FQ_E_UNSUPPORTED "cast produced
+ * nulls".
+ *
+ * When every column, step, comparison and output type is 64-bit each call IS
+ * its *_columns twin (same source, same shape key).  Any other shape runs on
+ * hipRTC-specialised kernels only (FQ_E_UNSUPPORTED with FQ_JIT_OFF or without
+ * hipRTC); fq_jit_prepare_project_typed compiles the shape's one module (all
+ * its kernels) ahead of time and, without a GPU, validates the generated
+ * source by compiling it for gfx950.  The workspace of fq_filter_project_typed
+ * holds one look-back status word per tile of the typed kernel, whose rows
+ * depend on the columns' widths: fq_filter_project_typed_workspace_bytes.    */
+size_t fq_filter_project_typed_workspace_bytes(int64_t len, const fq_col *cols, int32_t n_cols);
+fq_status fq_filter_project_typed(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const fq_expr *values,
+                                  int32_t n_out, void *const *d_out, int64_t *out_len, void *d_ws, size_t ws_bytes,
+                                  void *stream);
+fq_status fq_filter_project_blocks_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                         const fq_expr *values, int32_t n_out, void *const *d_out, int64_t *d_counts,
+                                         int64_t *out_len, void *d_ws, size_t ws_bytes, void *stream);
+fq_status fq_predicate_bitmap_typed(const fq_col *cols, int32_t n_cols, const fq_pred *pred, uint64_t *d_bitmap,
+                                    uint32_t *d_flag, void *stream);
+fq_status fq_jit_prepare_project_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
+                                       const fq_expr *values, int32_t n_out, int32_t *specialised);
+
 /* ---- AggregateFinal state merge (host, function_aggregator.rs:106-139) ----
  * Merges `n` partial states in the given order into *out (wrapping sum,
  * summed counts/blocks, max, min, OR-ed flags).  All dtypes must match.      */

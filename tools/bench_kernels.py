@@ -11,6 +11,7 @@ usage: python tools/bench_kernels.py [--rows 1.25e9] [--reps 10] > gpurun_out/ke
        python tools/bench_kernels.py --only q6 [--q6-rows 134217728] [--reps 20]   (the q6 lines alone)
        python tools/bench_kernels.py --only pcols [--q6-rows 134217728] [--reps 20]   (Filter -> Projection over 3 columns)
        python tools/bench_kernels.py --only typed [--q6-rows 134217728] [--reps 20]   (the Q6 shape over narrow columns)
+       python tools/bench_kernels.py --only ptyped [--q6-rows 134217728] [--reps 20]   (Filter -> Projection over them)
 """
 import argparse
 import ctypes as C
@@ -397,18 +398,161 @@ def typed_lines(n, reps, st, res):
         "typed_below_widened": {"flat": bool(med(t_flat) < med(w_flat)), "block_mode": bool(med(t_blk) < med(w_blk))}}})
 
 
+def ptyped_lines(n, reps, st, res):
+    """SELECT price * discount, quantity WHERE shipdate < k and quantity < q over price Float64, discount Float32,
+    shipdate Int32, quantity UInt8 (17 B read + 9 B written per kept row, about 3/8 of the rows kept): ONE
+    fq_filter_project_blocks_typed / fq_filter_project_typed launch, beside -- in the same process -- the same
+    statement over the four columns widened to 64 bits through the *_columns entry points (32 B + 16 B per kept
+    row) and the unfused path for the narrow block (what ProjectionTransform runs when the shape does not fuse,
+    the parent commit's only path for it: two fq_compare, fq_logic, fq_filter_compact of the projected columns,
+    fq_arith on the kept rows).  Every launch event-timed; the entry points synchronise their stream for the
+    kept-row count, so each sample holds that host sync too."""
+    from fq_amd.expr import Col, chain_columns, load, pred_tree_columns
+    F64, F32, I32, U8, I64, U64 = (abi.DT_FLOAT64, abi.DT_FLOAT32, abi.DT_INT32, abi.DT_UINT8, abi.DT_INT64,
+                                   abi.DT_UINT64)
+    K, Q = 9950, 26  # shipdate in [8000, 10600): 3/4 below K; quantity in [1, 50]: 1/2 below Q
+    g = torch.Generator(device="cuda")
+    g.manual_seed(9)  # typed_lines' generator
+    t_price = torch.rand(n, dtype=torch.float64, device="cuda", generator=g) * 999.0 + 1.0
+    t_disc = torch.randint(0, 11, (n,), device="cuda", generator=g).to(torch.float32) / 100.0
+    t_ship = torch.randint(8000, 10600, (n,), dtype=torch.int32, device="cuda", generator=g)
+    t_qty = torch.randint(1, 51, (n,), dtype=torch.uint8, device="cuda", generator=g)
+
+    def column(t, dt):
+        return ops.DeviceColumn(t.view(torch.uint8), n, dt)
+
+    narrow = [column(t_price, F64), column(t_disc, F32), column(t_ship, I32), column(t_qty, U8)]
+    ndts = [F64, F32, I32, U8]
+    wide_t = [t_price, t_disc.to(torch.float64), t_ship.to(torch.int64), t_qty.to(torch.int64)]
+    wdts = [F64, F64, I64, U64]
+    wide = [column(t, dt) for t, dt in zip(wide_t, wdts)]
+
+    def program(dts, kt, qt):
+        pred = pred_tree_columns(dts, [([load(2)], "<", (K, kt)), ([load(3)], "<", (Q, qt))], [0, 1, "and"])
+        vals = (abi.fq_expr * 2)(chain_columns(dts, [("*", Col(1))])[0], chain_columns(dts, [load(3)])[0])
+        assert vals[0].out_dtype == F64 and vals[1].out_dtype == dts[3]
+        return pred, vals
+
+    npred, nvals = program(ndts, "Int32", "UInt8")
+    wpred, wvals = program(wdts, "Int64", "UInt64")
+    ncols = (abi.fq_col * 4)(*[c.col() for c in narrow])
+    wcols = (abi.fq_col * 4)(*[c.col() for c in wide])
+    o_prod, o_qty, o_wqty = ops.empty_column(n, F64), ops.empty_column(n, U8), ops.empty_column(n, U64)
+    nouts = (C.c_void_p * 2)(o_prod.ptr, o_qty.ptr)
+    wouts = (C.c_void_p * 2)(o_prod.ptr, o_wqty.ptr)
+    B = 10000
+    nb = -(-n // B)
+    counts = ops.Workspace(8 * nb)
+    bws = ops.Workspace(lib.fq_filter_project_blocks_workspace_bytes())
+    tws = ops.Workspace(lib.fq_filter_project_typed_workspace_bytes(n, ncols, 4))
+    cws = ops.Workspace(lib.fq_filter_project_columns_workspace_bytes(n, 4))
+    kept = C.c_int64(0)
+
+    def rec(name, ts, nbytes, note=""):
+        ms = statistics.median(ts)
+        gbps = nbytes / (ms * 1e-3) / 1e9
+        res.append({"kernel": name, "ms": ms, "ms_min": min(ts), "ms_max": max(ts), "reps": len(ts),
+                    "algorithmic_bytes": nbytes, "achieved_gbps": gbps, "frac_of_peak": gbps / PEAK, "note": note})
+        print("%-58s %8.3f ms [%.3f .. %.3f]  %7.0f GB/s  %4.1f %%" % (name, ms, min(ts), max(ts), gbps,
+                                                                     100 * gbps / PEAK), file=sys.stderr)
+        return ts
+
+    keep = (t_ship < K) & (t_qty < Q)
+    m = int(keep.sum())
+    want_prod = (t_price[keep] * t_disc[keep].to(torch.float64)).view(torch.int64)
+    want_qty = t_qty[keep]
+    k0 = int(keep[:B].sum())
+
+    def out_t(col, dtype, rows):
+        return col.buf[col.offset:col.offset + rows * torch.empty(0, dtype=dtype).element_size()].view(dtype)
+
+    def verify(what, qty_col, qty_dtype, rows):
+        """the first `rows` output rows against torch (block geometry: block 0's kept rows)"""
+        assert kept.value == m, (what, kept.value, m)
+        assert torch.equal(out_t(o_prod, torch.int64, rows), want_prod[:rows]), what
+        assert torch.equal(out_t(qty_col, qty_dtype, rows).to(torch.uint8), want_qty[:rows]), what
+
+    def typed_blocks():
+        check(lib.fq_filter_project_blocks_typed(ncols, 4, B, C.byref(npred), nvals, 2, nouts, counts.ptr, C.byref(kept),
+                                                 bws.ptr, bws.nbytes, st))
+
+    def typed_contiguous():
+        check(lib.fq_filter_project_typed(ncols, 4, C.byref(npred), nvals, 2, nouts, C.byref(kept), tws.ptr, tws.nbytes, st))
+
+    def wide_blocks():
+        check(lib.fq_filter_project_blocks_columns(wcols, 4, B, C.byref(wpred), wvals, 2, wouts, counts.ptr, C.byref(kept),
+                                                   bws.ptr, bws.nbytes, st))
+
+    def wide_contiguous():
+        check(lib.fq_filter_project_columns(wcols, 4, C.byref(wpred), wvals, 2, wouts, C.byref(kept), cws.ptr, cws.nbytes, st))
+
+    t_blk = rec("ptyped price*discount, quantity, 10,000-row blocks", timed_all(typed_blocks, reps), 17 * n + 9 * m,
+                "fq_filter_project_blocks_typed over f64 f32 i32 u8 columns: 17 B read + 9 B per kept row")
+    verify("typed blocks", o_qty, torch.uint8, k0)
+    assert int(counts.buf[:8].view(torch.int64)[0]) == k0
+    t_con = rec("ptyped price*discount, quantity, contiguous", timed_all(typed_contiguous, reps), 17 * n + 9 * m,
+                "fq_filter_project_typed (look-back kernel)")
+    verify("typed contiguous", o_qty, torch.uint8, m)
+    w_blk = rec("widened to 4 64-bit columns, 10,000-row blocks", timed_all(wide_blocks, reps), 32 * n + 16 * m,
+                "fq_filter_project_blocks_columns: 32 B read + 16 B per kept row")
+    verify("widened blocks", o_wqty, torch.int64, k0)
+    w_con = rec("widened to 4 64-bit columns, contiguous", timed_all(wide_contiguous, reps), 32 * n + 16 * m,
+                "fq_filter_project_columns")
+    verify("widened contiguous", o_wqty, torch.int64, m)
+
+    # the unfused path for the narrow block
+    bm1, bm2, bm = (ops.empty_column(n, abi.DT_BOOLEAN) for _ in range(3))
+    k_price, k_disc = ops.empty_column(n, F64), ops.empty_column(n, F32)
+    fws = ops.Workspace(lib.fq_filter_workspace_bytes(n))
+    kv, qv = abi.fq_value(I32, 1, K), abi.fq_value(U8, 1, Q)
+    sc, qc = narrow[2].col(), narrow[3].col()
+
+    def unfused():
+        lt = abi.CMP_BY_SYM["<"]
+        check(lib.fq_compare(lt, C.byref(sc), None, None, C.byref(kv), C.c_void_p(bm1.ptr), n, None, st))
+        check(lib.fq_compare(lt, C.byref(qc), None, None, C.byref(qv), C.c_void_p(bm2.ptr), n, None, st))
+        check(lib.fq_logic(0, C.c_void_p(bm1.ptr), C.c_void_p(bm2.ptr), C.c_void_p(bm.ptr), n, st))
+        for src, out in ((narrow[0], k_price), (narrow[1], k_disc), (narrow[3], o_qty)):
+            c = src.col()
+            check(lib.fq_filter_compact(C.byref(c), C.c_void_p(bm.ptr), C.c_void_p(out.ptr), C.byref(kept), fws.ptr,
+                                        fws.nbytes, st))
+        k = kept.value
+        lc = abi.fq_col(C.c_void_p(k_price.ptr), k, F64, 0)
+        rc = abi.fq_col(C.c_void_p(k_disc.ptr), k, F32, 0)
+        oc = abi.fq_col(C.c_void_p(o_prod.ptr), k, F64, 0)
+        check(lib.fq_arith(abi.OP_BY_SYM["*"], C.byref(lc), None, C.byref(rc), None, C.byref(oc), None, st))
+
+    ts = timed_all(unfused, reps)
+    verify("unfused", o_qty, torch.uint8, m)
+    bits = n // 8
+    moved = (4 * n + bits) + (n + bits) + 3 * bits + (13 * n + 3 * bits + 13 * m) + 20 * m
+    u = rec("ptyped unfused: 2 compare, and, 3 compactions, arith", ts, moved,
+            "seven launches; includes fq_filter_compact's host syncs; bytes = what the path moves")
+    med = statistics.median
+    res.append({"project_typed_q6": {
+        "rows": n, "kept_rows": m, "bytes": {"typed": 17 * n + 9 * m, "widened": 32 * n + 16 * m},
+        "typed_tb_per_s": {"block_stream": (17 * n + 9 * m) / (med(t_blk) * 1e-3) / 1e12,
+                           "contiguous": (17 * n + 9 * m) / (med(t_con) * 1e-3) / 1e12},
+        "unfused_over_typed": {"block_stream": med(u) / med(t_blk), "contiguous": med(u) / med(t_con)},
+        "widened_over_typed": {"block_stream": med(w_blk) / med(t_blk), "contiguous": med(w_con) / med(t_con),
+                               "bytes_ratio": (32 * n + 16 * m) / (17 * n + 9 * m)},
+        "typed_below_unfused_non_overlapping": bool(max(t_blk) < min(u) and max(t_con) < min(u)),
+        "typed_below_widened": {"block_stream": bool(med(t_blk) < med(w_blk)), "contiguous": bool(med(t_con) < med(w_con))}}})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=float, default=1.25e9)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--only", choices=["q6", "pcols", "typed"], default=None, help="run only the named group of lines")
+    ap.add_argument("--only", choices=["q6", "pcols", "typed", "ptyped"], default=None, help="run only the named group of lines")
     ap.add_argument("--q6-rows", type=float, default=float(1 << 27))
     args = ap.parse_args()
     n = int(args.rows)
     st = ops._stream()
     res = []
-    if args.only in ("q6", "pcols", "typed"):
-        {"q6": q6_lines, "pcols": pcols_lines, "typed": typed_lines}[args.only](int(args.q6_rows), args.reps, st, res)
+    if args.only in ("q6", "pcols", "typed", "ptyped"):
+        {"q6": q6_lines, "pcols": pcols_lines, "typed": typed_lines, "ptyped": ptyped_lines}[args.only](
+            int(args.q6_rows), args.reps, st, res)
         print(json.dumps({"rows": int(args.q6_rows), "peak_gbps": PEAK, "device": torch.cuda.get_device_name(0),
                           "kernels": res}, indent=1))
         return
@@ -586,6 +730,7 @@ def main():
 
     q6_lines(int(args.q6_rows), args.reps, st, res)
     typed_lines(int(args.q6_rows), args.reps, st, res)
+    ptyped_lines(int(args.q6_rows), args.reps, st, res)
 
     print(json.dumps({"rows": n, "peak_gbps": PEAK, "device": torch.cuda.get_device_name(0),
                       "kernels": res}, indent=1))

@@ -264,6 +264,38 @@ fq_status fq_functions_accumulate(fq_engine *e, fq_function *const *fs, int32_t 
     });
 }
 
+fq_status fq_functions_accumulate_nullable(fq_engine *e, fq_function *const *fs, int32_t n, const fq_block *b,
+                                           const uint64_t *const *validity) {
+    if (!e || !b || n < 0 || (n > 0 && !fs) || !validity)
+        return fqc::fail(FQ_E_INVALID, "fq_functions_accumulate_nullable: bad argument");
+    for (int32_t i = 0; i < n; ++i)
+        if (!fs[i]) return fqc::fail(FQ_E_INVALID, "fq_functions_accumulate_nullable: NULL function");
+    return guard([&] {
+        fq::ExecCtx ctx(device_runtime(e));
+        const fq::DataBlock blk = borrow_block(*b);
+        std::vector<std::pair<std::string, const uint64_t *>> vb;
+        for (int32_t i = 0; i < b->n_columns; ++i) {
+            if (((uintptr_t)validity[i]) % 8)
+                throw fq::FQException(FQ_E_INVALID, "fq_functions_accumulate_nullable: validity bitmap " +
+                                                        std::to_string(i) + " not aligned to 8 bytes");
+            vb.emplace_back(b->names[i], validity[i]);
+        }
+        // fq_functions_accumulate's loop, every scan an fq_aggregate_nullable
+        fq::AggFusion fusion(ctx);
+        fusion.set_validity(std::move(vb));
+        fq::AggFusion *prev = ctx.fusion;
+        ctx.fusion = &fusion;
+        try {
+            for (int32_t i = 0; i < n; ++i) fs[i]->f->accumulate(blk, ctx);
+        } catch (...) {
+            ctx.fusion = prev;
+            throw;
+        }
+        ctx.fusion = prev;
+        fusion.finish();
+    });
+}
+
 }  // extern "C"
 
 namespace {

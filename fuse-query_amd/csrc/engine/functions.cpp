@@ -486,6 +486,37 @@ void AggregatorFunction::accumulate_summary(const fq_agg_state &st) {
     }
 }
 
+// A nullable scan's state (fq_aggregate_nullable): count = the kept rows, nulls
+// included; a block's min / max / sum is None when it has no valid kept value.
+// Casts that overflow are nulls here, so FQ_STATE_CAST_NULL never arrives.
+void AggregatorFunction::accumulate_summary(const fq_agg_state_n &sn) {
+    const fq_agg_state &st = sn.s;
+    if (st.blocks == 0) return;
+    if (st.flags & FQ_STATE_DIV_ZERO) throw_status(FQ_E_DIVIDE_BY_ZERO, "Internal Error: Divide by zero error");
+    switch (op_) {
+        case FQ_AGG_COUNT:
+            state_ = data_value_arithmetic_op(FQ_OP_ADD, state_, DataValue::u64(st.count));
+            return;
+        case FQ_AGG_MIN:
+        case FQ_AGG_MAX: {
+            const DataValue d = sn.valid ? DataValue::some(st.dtype, op_ == FQ_AGG_MAX ? st.max : st.min)
+                                         : DataValue::none(st.dtype);
+            state_ = data_value_aggregate_op(op_, state_, d);
+            return;
+        }
+        default: {
+            if (st.blocks == 1) {
+                const DataValue d = sn.valid ? DataValue::some(st.dtype, st.sum) : DataValue::none(st.dtype);
+                state_ = data_value_arithmetic_op(FQ_OP_ADD, state_, d);
+                return;
+            }
+            if (st.flags & FQ_STATE_ANY_EMPTY) throw_internal("DataValue to array cannot be NONE NULL");
+            state_ = data_value_arithmetic_op(FQ_OP_ADD, state_, DataValue::some(st.dtype, st.sum));
+            return;
+        }
+    }
+}
+
 static uint32_t scan_mask(uint32_t op) { return op | FQ_AGG_COUNT; }
 
 static fq_agg_state run_scan(const Column &col, int64_t block_rows, const fq_pred *pred, const fq_expr *value,
@@ -1230,6 +1261,19 @@ size_t AggFusion::alloc_slot() {
     return k;
 }
 
+size_t AggFusion::alloc_slot_n() {
+    static_assert(WorkerRes::kSlotChunk % 2 == 0 && 2 * sizeof(fq_agg_state) >= sizeof(fq_agg_state_n), "slot pairs");
+    if (nslots_ % 2) alloc_slot();  // pairs never straddle a chunk
+    const size_t k = alloc_slot();
+    alloc_slot();
+    return k;
+}
+
+void AggFusion::set_validity(std::vector<std::pair<std::string, const uint64_t *>> validity) {
+    nullable_ = true;
+    validity_ = std::move(validity);
+}
+
 void AggFusion::wait_launched() {
     hipEvent_t done = res_->take_sync_event();
     {
@@ -1248,7 +1292,72 @@ void AggFusion::add_error(const FQException &e) {
     log_.push_back(en);
 }
 
+// A nullable block: the column list add() builds (the filter's columns, then
+// the argument's), always as one fq_aggregate_nullable scan.
+void AggFusion::add_nullable(AggregatorFunction *agg, const DataBlock &b) {
+    const DataSchema &s = *b.schema;
+    auto unsupported = [](const std::string &why) {
+        throw FQException(FQ_E_UNSUPPORTED, "fq_functions_accumulate_nullable: " + why +
+                                                " (there is no unfused path over nullable columns)");
+    };
+    if (!tree_fusion_enabled()) unsupported("the hipRTC kernels are off (FQ_JIT_OFF) or unavailable");
+    FusedChain fc;
+    FusedPred fp;
+    FusedColumns cols;
+    cols.typed = true;
+    if (b.filter && !b.filter->to_pred(s, fp, &cols))
+        unsupported("the filter does not fuse (more than " + std::to_string(FQ_MAX_SCAN_COLS) +
+                    " columns, a non-numeric column, or an expression outside the fused forms)");
+    if (!agg->arg().to_chain(s, fc, &cols))
+        unsupported("the argument does not fuse (more than " + std::to_string(FQ_MAX_SCAN_COLS) +
+                    " columns, a non-numeric column, or an expression outside the fused forms)");
+    fq_expr value_expr = fc.expr;
+    // the nullable lowering adds no step to the lowered programs: typed_scan_fits is its dry run too
+    if (!fc.with_load(value_expr) ||
+        !fqk::typed_scan_fits(cols.dtypes.data(), (int32_t)cols.names.size(), b.filter ? fp.get() : nullptr,
+                              value_expr.n_steps ? &value_expr : nullptr))
+        unsupported("the expression does not fit a fused scan's step budget");
+    for (const std::string &name : cols.names)
+        if (!b.column_by_name(name).on_device()) unsupported("column " + name + " is not on the device");
+    fc.columns = fp.columns = cols.names;
+    const std::string key = fc.key() + "|" + (b.filter ? fp.key() : std::string());
+    Group *g = nullptr;
+    for (auto &x : cur_)
+        if (x.key == key) g = &x;
+    if (!g) {
+        cur_.emplace_back();
+        g = &cur_.back();
+        g->key = key;
+        g->col = b.column_by_name(cols.names[0]);
+        g->typed = g->nullable = true;
+        for (const std::string &name : cols.names) {
+            g->cols.push_back(b.column_by_name(name));
+            const uint64_t *vb = nullptr;
+            for (const auto &v : validity_)
+                if (v.first == name) vb = v.second;
+            g->validity.push_back(vb);
+        }
+        g->value = fc;
+        g->value_expr = value_expr;
+        g->has_pred = (bool)b.filter;
+        if (g->has_pred) g->pred = fp;
+        g->filter_keepalive = b.filter;
+        const int64_t rows = g->col.len;
+        g->block_rows = b.sub_block_rows > 0 ? b.sub_block_rows : (rows > 0 ? rows : 1);
+        g->blocks = b.sub_blocks();
+        g->slot = alloc_slot_n();
+    }
+    g->mask |= scan_mask(agg->op());
+    Entry en;
+    en.agg = agg;
+    en.slot = g->slot;
+    en.nullable = true;
+    en.st.blocks = g->blocks;
+    log_.push_back(en);
+}
+
 void AggFusion::add(AggregatorFunction *agg, const DataBlock &b) {
+    if (nullable_) return add_nullable(agg, b);
     const DataSchema &s = *b.schema;
     FusedChain fc;
     FusedPred fp;
@@ -1343,7 +1452,15 @@ void AggFusion::end_block() {
             e0 = ctx_.res->take_event();
             e1 = ctx_.res->take_event();
         }
-        if (prof && n_cols) {
+        const uint64_t *vb[FQ_MAX_SCAN_COLS] = {};
+        uint8_t has_vb[FQ_MAX_SCAN_COLS] = {};
+        for (size_t j = 0; j < g.validity.size(); ++j) vb[j] = g.validity[j], has_vb[j] = g.validity[j] ? 1 : 0;
+        if (g.nullable && !ws_n_)
+            ws_n_ = DeviceBuffer::alloc(fq_aggregate_nullable_workspace_bytes(g.col.len), stream_);
+        if (prof && g.nullable) {
+            check_fq(fq_jit_prepare_nullable(cs, has_vb, n_cols, g.block_rows, g.has_pred ? g.pred.get() : nullptr,
+                                             g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask, nullptr));
+        } else if (prof && n_cols) {
             check_fq((g.typed ? fq_jit_prepare_typed : fq_jit_prepare_columns)(
                 cs, n_cols, g.block_rows, g.has_pred ? g.pred.get() : nullptr,
                 g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask, nullptr));
@@ -1364,7 +1481,12 @@ void AggFusion::end_block() {
             const fq_expr *val = g.value.expr.n_steps ? &g.value.expr : nullptr;
             if (ticket_ && ticket_->group()) ticket_->group()->before_launch(ctx_);
             if (pairs) check_hip(hipEventRecord(e0, stream_), "hipEventRecord");
-            if (n_cols)
+            if (g.nullable)
+                check_fq(fq_aggregate_nullable(cs, vb, n_cols, g.block_rows, pred,
+                                               g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask,
+                                               (fq_agg_state_n *)dst, ws_n_->ptr,
+                                               fq_aggregate_nullable_workspace_bytes(g.col.len), stream_));
+            else if (n_cols)
                 check_fq((g.typed ? fq_aggregate_typed : fq_aggregate_columns)(
                     cs, n_cols, g.block_rows, pred, g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask,
                     (fq_agg_state *)dst, res_->ws, res_->ws_bytes, stream_));
@@ -1383,6 +1505,8 @@ void AggFusion::end_block() {
         uint64_t row_bytes = n_cols ? 0 : (uint64_t)dtype_size(g.col.dtype);
         for (const Column &gc : g.cols) row_bytes += (uint64_t)dtype_size(gc.dtype);
         ctx_.rt->stats.scan_bytes += (uint64_t)g.col.len * row_bytes;
+        for (const uint64_t *v : g.validity)  // and a bit per row of every bitmap
+            if (v) ctx_.rt->stats.scan_bytes += ((uint64_t)g.col.len + 7) / 8;
         // a stream-ordered column (hipFreeAsync on the queue the scan was just
         // enqueued on) may be dropped now: its memory returns to the pool only
         // after the scan -- so a query over generated chunks holds one chunk per
@@ -1430,6 +1554,13 @@ void AggFusion::replay() {
     std::vector<char> have(nslots_, 0);
     for (Entry &en : log_) {
         if (en.has_error) throw en.err;
+        if (en.nullable) {
+            fq_agg_state_n sn;
+            memcpy(&sn, slot_host(en.slot), sizeof sn);
+            sn.s.blocks = en.st.blocks;
+            en.agg->accumulate_summary(sn);
+            continue;
+        }
         fq_agg_state st = en.st;
         if (en.slot != (size_t)-1) {
             if (!have[en.slot]) {

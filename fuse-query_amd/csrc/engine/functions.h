@@ -298,6 +298,8 @@ class AggregatorFunction : public Function {
     // Replays the reference's per-block accumulate over a run of `st.blocks`
     // reference blocks summarised by one device scan (see fq_agg_state).
     void accumulate_summary(const fq_agg_state &st);
+    // the same over a nullable scan's state: Min/Max/Sum hold a value iff st.valid > 0
+    void accumulate_summary(const fq_agg_state_n &st);
     // Non-deferred evaluation of this aggregator over one block.
     fq_agg_state summarize(const DataBlock &b, ExecCtx &ctx);
 
@@ -441,6 +443,11 @@ class AggFusion {
    public:
     explicit AggFusion(ExecCtx &ctx, ScanTicket *ticket = nullptr);
     ~AggFusion();
+    // fq_functions_accumulate_nullable: the blocks' columns carry these Arrow
+    // validity bitmaps (by column name; null: every row valid).  Every scan is
+    // then one fq_aggregate_nullable; a shape that does not fuse is an error
+    // (there is no unfused path over nulls).
+    void set_validity(std::vector<std::pair<std::string, const uint64_t *>> validity);
     void add(AggregatorFunction *agg, const DataBlock &b);
     void add_error(const FQException &e);  // a non-aggregator failure at this point
     void end_block();                      // launch this block's scans
@@ -458,6 +465,8 @@ class AggFusion {
         Column col;
         std::vector<Column> cols;  // more than one column: fq_aggregate_columns
         bool typed = false;        // a narrow column, step or comparison: fq_aggregate_typed over cols (one or more)
+        bool nullable = false;     // fq_aggregate_nullable over cols and validity; the slot holds an fq_agg_state_n
+        std::vector<const uint64_t *> validity;
         fq_expr value_expr{};      // value.expr, FQ_OP_LOAD in front when it starts from another column than 0
         FusedChain value;
         bool has_pred = false;
@@ -471,6 +480,7 @@ class AggFusion {
     struct Entry {
         AggregatorFunction *agg = nullptr;
         size_t slot = (size_t)-1;  // device result slot, or
+        bool nullable = false;     // (the slot holds an fq_agg_state_n)
         fq_agg_state st{};         // an immediate summary
         bool has_error = false;
         FQException err{0, ""};
@@ -489,7 +499,12 @@ class AggFusion {
     size_t nslots_ = 0;
     bool launched_ = false, finished_ = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events_;
+    bool nullable_ = false;
+    std::vector<std::pair<std::string, const uint64_t *>> validity_;
+    std::shared_ptr<DeviceBuffer> ws_n_;  // the nullable scans' workspace (64-byte partials)
+    void add_nullable(AggregatorFunction *agg, const DataBlock &b);
     size_t alloc_slot();
+    size_t alloc_slot_n();  // an fq_agg_state_n: two neighbouring slots of one chunk
     fq_agg_state *slot_host(size_t k) const;
     void wait_launched();
 };

@@ -338,6 +338,50 @@ __global__ void __launch_bounds__(kThreads)
     fold_partials<V>(parts, nparts, blocks, rows, vdtype, empty_if_zero, out);
 }
 
+// fq_aggregate_nullable: the same fold over the scan's PartialN, and their
+// valid counts (integers: any order).  A single reference block is empty when
+// it has no valid kept value; nparts == 0 is the count-only call, which reads
+// no value.
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    agg_finalize_nullable_kernel(const PartialN *parts, int nparts, uint64_t blocks, uint64_t rows, int32_t vdtype,
+                                 int empty_if_zero, fq_agg_state_n *out) {
+    Acc<V> acc;
+    acc.init();
+    if (threadIdx.x == 0) acc.cnt = rows;
+    unsigned long long valid = 0;
+    for (int i = threadIdx.x; i < nparts; i += kThreads) {
+        const PartialN q = parts[i];
+        acc.sum = acc.sum + from_bits<V>(q.p.sum);
+        acc.mx = vmax(acc.mx, from_bits<V>(q.p.max));
+        acc.mn = vmin(acc.mn, from_bits<V>(q.p.min));
+        acc.cnt += q.p.count;
+        acc.flags |= q.p.flags;
+        valid += q.valid;
+    }
+    __shared__ Partial s_out;
+    __shared__ unsigned long long s_valid;
+    if (threadIdx.x == 0) s_valid = 0;
+    __syncthreads();
+    atomicAdd(&s_valid, valid);
+    reduce_and_store<V>(acc, &s_out, vdtype);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        fq_agg_state_n r;
+        r.s.sum = s_out.sum;
+        r.s.max = s_out.max;
+        r.s.min = s_out.min;
+        r.s.count = s_out.count;
+        r.s.blocks = blocks;
+        r.s.flags = s_out.flags;
+        if (empty_if_zero && nparts > 0 && s_valid == 0) r.s.flags |= FQ_STATE_ANY_EMPTY;
+        r.s.dtype = vdtype;
+        r.valid = s_valid;
+        r.reserved = 0;
+        *out = r;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host-side lowering and dispatch
 // ---------------------------------------------------------------------------
@@ -824,6 +868,31 @@ static fq_status dispatch(int32_t col_dt, const Launch &L, bool chain) {
                                            " value is not supported on the device path");
 }
 
+template <typename V>
+static fq_status launch_finalize_nullable(const Launch &L, uint64_t blocks, int empty_if_zero, fq_agg_state_n *d_out) {
+    hipLaunchKernelGGL((agg_finalize_nullable_kernel<V>), dim3(1), dim3(kThreads), 0, L.stream,
+                       (const PartialN *)L.parts, L.grid, blocks, L.grid == 0 ? (uint64_t)L.n : 0ull, L.vdtype,
+                       empty_if_zero, d_out);
+    FQ_HIP_TRY(hipGetLastError());
+    return FQ_OK;
+}
+
+static fq_status dispatch_finalize_nullable(const Launch &L, uint64_t blocks, int empty_if_zero, fq_agg_state_n *d_out) {
+    switch (L.vdtype) {
+        case FQ_DT_INT8: return launch_finalize_nullable<int8_t>(L, blocks, empty_if_zero, d_out);
+        case FQ_DT_INT16: return launch_finalize_nullable<int16_t>(L, blocks, empty_if_zero, d_out);
+        case FQ_DT_INT32: return launch_finalize_nullable<int32_t>(L, blocks, empty_if_zero, d_out);
+        case FQ_DT_INT64: return launch_finalize_nullable<int64_t>(L, blocks, empty_if_zero, d_out);
+        case FQ_DT_UINT8: return launch_finalize_nullable<uint8_t>(L, blocks, empty_if_zero, d_out);
+        case FQ_DT_UINT16: return launch_finalize_nullable<uint16_t>(L, blocks, empty_if_zero, d_out);
+        case FQ_DT_UINT32: return launch_finalize_nullable<uint32_t>(L, blocks, empty_if_zero, d_out);
+        case FQ_DT_UINT64: return launch_finalize_nullable<uint64_t>(L, blocks, empty_if_zero, d_out);
+        case FQ_DT_FLOAT32: return launch_finalize_nullable<float>(L, blocks, empty_if_zero, d_out);
+        case FQ_DT_FLOAT64: return launch_finalize_nullable<double>(L, blocks, empty_if_zero, d_out);
+        default: return fqc::fail(FQ_E_INVALID, "finalize: bad dtype");
+    }
+}
+
 static fq_status dispatch_finalize(const Launch &L, uint64_t blocks, int empty_if_zero, fq_agg_state *d_out) {
     switch (L.vdtype) {
         case FQ_DT_INT8: return launch_finalize<int8_t>(L, blocks, empty_if_zero, d_out);
@@ -1129,11 +1198,12 @@ bool call_is_64(const fq_col *cols, int32_t n_cols, const fq_pred *pred, const f
 
 static fq_status plan_scan_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
                                  const fq_expr *value, uint32_t agg_mask, bool need_data, Launch &L, bool &chain,
-                                 uint64_t &blocks, int &empty_if_zero) {
+                                 uint64_t &blocks, int &empty_if_zero, bool nullable = false) {
     const int64_t len = cols[0].len;
     if (block_rows <= 0) block_rows = len > 0 ? len : 1;
     L = Launch{};
     L.typed = true;
+    L.nullable = nullable;
     L.col = cols[0].data;
     L.n = len;
     L.block_rows = block_rows;
@@ -1156,6 +1226,10 @@ static fq_status plan_scan_typed(const fq_col *cols, int32_t n_cols, int64_t blo
     blocks = len == 0 ? 0 : (uint64_t)((len + block_rows - 1) / block_rows);
     L.block_mode = L.pred.kind != FQ_PRED_NONE && (agg_mask & FQ_AGG_SUM) && blocks > 1;
     empty_if_zero = (L.pred.kind != FQ_PRED_NONE && blocks == 1) ? 1 : 0;
+    if (nullable) {  // an unfiltered block whose values are all null is a None sum too
+        L.block_mode = (agg_mask & FQ_AGG_SUM) && blocks > 1;
+        empty_if_zero = blocks == 1 ? 1 : 0;
+    }
 
     typed_group(L.cdt, n_cols, &L.group, &L.prefetch);
     const int64_t G = L.group;
@@ -1246,6 +1320,71 @@ fq_status fq_jit_prepare_typed(const fq_col *cols, int32_t n_cols, int64_t block
     int empty_if_zero = 0;
     s = plan_scan_typed(cols, n_cols, block_rows, pred, value, agg_mask, false, L, chain, blocks, empty_if_zero);
     if (s != FQ_OK) return s;
+    bool ok = false;
+    s = jit_prepare(cols[0].dtype, chain, L, &ok);
+    if (s != FQ_OK) return s;
+    if (!ok) return fqc::fail(FQ_E_UNSUPPORTED, kTypedNeedsJit);
+    if (specialised) *specialised = 1;
+    return FQ_OK;
+}
+
+size_t fq_aggregate_nullable_workspace_bytes(int64_t len) {
+    (void)len;
+    return (size_t)fqk::kMaxPartials * sizeof(fqk::PartialN);
+}
+
+fq_status fq_aggregate_nullable(const fq_col *cols, const uint64_t *const *validity, int32_t n_cols,
+                                int64_t block_rows, const fq_pred *pred, const fq_expr *value, uint32_t agg_mask,
+                                fq_agg_state_n *d_out, void *d_ws, size_t ws_bytes, void *stream) {
+    using namespace fqk;
+    fq_status s = check_cols_typed(cols, n_cols, true, "fq_aggregate_nullable");
+    if (s != FQ_OK) return s;
+    if (!validity || !d_out || !d_ws) return fqc::fail(FQ_E_INVALID, "fq_aggregate_nullable: NULL argument");
+    for (int j = 0; j < n_cols; ++j)
+        if (((uintptr_t)validity[j]) % 8)
+            return fqc::fail(FQ_E_INVALID, "fq_aggregate_nullable: validity bitmap " + std::to_string(j) +
+                                               " not aligned to 8 bytes");
+    if (ws_bytes < fq_aggregate_nullable_workspace_bytes(cols[0].len))
+        return fqc::fail(FQ_E_INVALID, "fq_aggregate_nullable: workspace too small");
+    if (agg_mask & ~(uint32_t)(FQ_AGG_MIN | FQ_AGG_MAX | FQ_AGG_SUM | FQ_AGG_COUNT))
+        return fqc::fail(FQ_E_INVALID, "fq_aggregate_nullable: unknown bits in agg_mask");
+    Launch L;
+    bool chain = false;
+    uint64_t blocks = 0;
+    int empty_if_zero = 0;
+    s = plan_scan_typed(cols, n_cols, block_rows, pred, value, agg_mask, true, L, chain, blocks, empty_if_zero, true);
+    if (s != FQ_OK) return s;
+    for (int j = 0; j < n_cols; ++j) {
+        L.validity[j] = validity[j];
+        L.has_bm[j] = validity[j] != nullptr;
+    }
+    L.stream = (hipStream_t)stream;
+    L.parts = (Partial *)d_ws;  // PartialN behind it (Launch::nullable)
+    if (agg_mask == FQ_AGG_COUNT && !chain && L.pred.kind == FQ_PRED_NONE) {
+        L.grid = 0;  // count(column): rows, nulls included -- neither the column nor its bitmap is read
+        return dispatch_finalize_nullable(L, blocks, empty_if_zero, d_out);
+    }
+    bool jitted = false;
+    s = jit_scan(cols[0].dtype, chain, L, &jitted, true);
+    if (s != FQ_OK) return s;
+    if (!jitted) return fqc::fail(FQ_E_UNSUPPORTED, kTypedNeedsJit);
+    return dispatch_finalize_nullable(L, blocks, empty_if_zero, d_out);
+}
+
+fq_status fq_jit_prepare_nullable(const fq_col *cols, const uint8_t *has_validity, int32_t n_cols, int64_t block_rows,
+                                  const fq_pred *pred, const fq_expr *value, uint32_t agg_mask,
+                                  int32_t *specialised) {
+    using namespace fqk;
+    if (specialised) *specialised = 0;
+    fq_status s = check_cols_typed(cols, n_cols, false, "fq_jit_prepare_nullable");
+    if (s != FQ_OK) return s;
+    Launch L;
+    bool chain = false;
+    uint64_t blocks = 0;
+    int empty_if_zero = 0;
+    s = plan_scan_typed(cols, n_cols, block_rows, pred, value, agg_mask, false, L, chain, blocks, empty_if_zero, true);
+    if (s != FQ_OK) return s;
+    for (int j = 0; j < n_cols; ++j) L.has_bm[j] = has_validity && has_validity[j];
     bool ok = false;
     s = jit_prepare(cols[0].dtype, chain, L, &ok);
     if (s != FQ_OK) return s;

@@ -107,6 +107,12 @@ struct Partial {
     int32_t dtype;
 };
 static_assert(sizeof(Partial) == sizeof(fq_agg_state), "partial layout");
+// fq_aggregate_nullable's per-workgroup partial; fq_agg_state_n's layout.
+struct PartialN {
+    Partial p;
+    uint64_t valid, reserved;
+};
+static_assert(sizeof(PartialN) == sizeof(fq_agg_state_n) && sizeof(PartialN) == 64, "nullable partial layout");
 
 // ---------------------------------------------------------------------------
 // value <-> 64-bit encoding (fq_value: ints sign/zero extended, floats binary64)

@@ -1105,16 +1105,45 @@ static_assert(FQ_STATE_CAST_NULL == 4u && FQ_STATE_DIV_ZERO == 2u, "the flag val
 struct TVal {
     std::string e;  // a variable of the generated source
     int32_t dt;
+    std::string v;  // nullable lowering: its validity, a u32 0 / 1 expression ("": always valid)
 };
 struct TGen {
     int uid = 0;
     int32_t cdt[FQ_MAX_SCAN_COLS] = {};
-    TVal X(int col) const { return TVal{"x" + std::to_string(col), cdt[col]}; }
+    // fq_aggregate_nullable: every value carries a validity; column j's is the
+    // parameter n<j> when it has a bitmap
+    bool nul = false;
+    bool has_bm[FQ_MAX_SCAN_COLS] = {};
+    TVal X(int col) const {
+        return TVal{"x" + std::to_string(col), cdt[col], nul && has_bm[col] ? "n" + std::to_string(col) : ""};
+    }
 };
 
 std::string tcast(const TVal &v, int32_t to) {
     if (v.dt == to) return v.e;
     return std::string("fq_cast<") + tname(to) + ">(" + v.e + ", flags, live)";
+}
+
+// Nullable lowering.  The AND of two validities, as a variable when both are expressions.
+std::string vand(TGen &g, std::string &body, const std::string &a, const std::string &b) {
+    if (a.empty() || b.empty() || a == b) return a.empty() ? b : a;
+    const std::string k = "k" + std::to_string(g.uid++);
+    body += "    const u32 " + k + " = " + a + " & " + b + ";\n";
+    return k;
+}
+// arrow's cast with nulls: fq_cast itself, its range check read from a flag word
+// of its own -- out of range is a null, never FQ_STATE_CAST_NULL
+TVal ncast(TGen &g, std::string &body, const TVal &v, int32_t to) {
+    if (v.dt == to) return v;
+    const std::string id = std::to_string(g.uid++);
+    const std::string T = tname(to);
+    if (to == FQ_DT_FLOAT32 || to == FQ_DT_FLOAT64) {
+        body += "    const " + T + " c" + id + " = (" + T + ")" + v.e + ";\n";
+        return TVal{"c" + id, to, v.v};
+    }
+    body += "    u32 cf" + id + " = 0u;\n    const " + T + " c" + id + " = fq_cast<" + T + ">(" + v.e + ", cf" + id +
+            ", 1u);\n    const u32 cv" + id + " = cf" + id + " == 0u ? 1u : 0u;\n";
+    return TVal{"c" + id, to, vand(g, body, v.v, "cv" + id)};
 }
 
 // Straight-line code for one lowered program; `cur` is acc before and after.
@@ -1129,6 +1158,10 @@ bool emit_prog_typed(TGen &g, std::string &body, const KProg &p, const std::stri
         switch (st.code) {
             case K_NOP: continue;
             case K_CAST:
+                if (g.nul) {
+                    cur = ncast(g, body, cur, st.dtype);
+                    continue;
+                }
                 body += decl + tcast(cur, st.dtype) + ";\n";
                 cur = TVal{t, st.dtype};
                 continue;
@@ -1139,8 +1172,19 @@ bool emit_prog_typed(TGen &g, std::string &body, const KProg &p, const std::stri
                 continue;
             default: break;
         }
-        std::string b;
-        if (st.operand == FQ_OPERAND_COLUMN) {
+        std::string a, b, valid;
+        if (g.nul && st.operand == FQ_OPERAND_STACK && stk.empty()) return false;
+        if (g.nul) {  // the operands' casts as statements: valid iff both operands are
+            TVal bv{std::string("fq_const<") + T + ">(c." + prefix + "[" + std::to_string(i) + "].c)", st.dtype, ""};
+            if (st.operand == FQ_OPERAND_COLUMN) bv = ncast(g, body, g.X(st.col), st.dtype);
+            if (st.operand == FQ_OPERAND_STACK) {
+                bv = ncast(g, body, stk.back(), st.dtype);
+                stk.pop_back();
+            }
+            const TVal av = ncast(g, body, cur, st.dtype);
+            a = av.e, b = bv.e;
+            valid = vand(g, body, av.v, bv.v);
+        } else if (st.operand == FQ_OPERAND_COLUMN) {
             b = tcast(g.X(st.col), st.dtype);
         } else if (st.operand == FQ_OPERAND_STACK) {
             if (stk.empty()) return false;
@@ -1149,7 +1193,7 @@ bool emit_prog_typed(TGen &g, std::string &body, const KProg &p, const std::stri
         } else {
             b = std::string("fq_const<") + T + ">(c." + prefix + "[" + std::to_string(i) + "].c)";
         }
-        const std::string a = tcast(cur, st.dtype);
+        if (!g.nul) a = tcast(cur, st.dtype);
         const std::string LR = st.reversed ? b + ", " + a : a + ", " + b;
         const char *fn = nullptr;
         bool flagged = false;
@@ -1168,8 +1212,10 @@ bool emit_prog_typed(TGen &g, std::string &body, const KProg &p, const std::stri
             case K_MOD_F: fn = "fq_mod", flagged = true; break;
             default: return false;  // typed lowering emits no constant-divisor magic
         }
-        body += decl + fn + "<" + T + ">(" + LR + (flagged ? ", flags, live" : "") + ");\n";
-        cur = TVal{t, st.dtype};
+        // a zero divisor raises only where both operands are valid (fq_div / fq_mod are total)
+        const std::string fl = valid.empty() ? ", flags, live" : ", flags, live & " + valid;
+        body += decl + fn + "<" + T + ">(" + LR + (flagged ? fl : "") + ");\n";
+        cur = TVal{t, st.dtype, valid};
     }
     return stk.empty();
 }
@@ -1183,6 +1229,15 @@ bool emit_leaf_typed(TGen &g, int32_t cmp, int32_t cmp_dtype, int32_t rhs_operan
     if (!op || !T) return false;
     TVal cur = g.X(0);
     if (!emit_prog_typed(g, body, lhs, prefix, cur)) return false;
+    if (g.nul) {  // n_<result>: the comparison is null if either side is
+        const TVal lv = ncast(g, body, cur, cmp_dtype);
+        TVal rv{std::string("fq_const<") + T + ">(" + rhs + ")", cmp_dtype, ""};
+        if (rhs_operand == FQ_OPERAND_COLUMN) rv = ncast(g, body, g.X(rhs_col), cmp_dtype);
+        const std::string valid = vand(g, body, lv.v, rv.v);
+        body += "    " + result + " = " + lv.e + " " + op + " " + rv.e + ";\n";
+        body += "    const u32 n_" + result + " = " + (valid.empty() ? std::string("1u") : valid) + ";\n";
+        return true;
+    }
     const std::string r = rhs_operand == FQ_OPERAND_COLUMN ? tcast(g.X(rhs_col), cmp_dtype)
                                                            : std::string("fq_const<") + T + ">(" + rhs + ")";
     const std::string l = "l" + std::to_string(g.uid++), rr = "r" + std::to_string(g.uid++);
@@ -1203,10 +1258,12 @@ bool emit_pred_typed(TGen &g, const KPred &pr, std::string &body) {
                 return false;
         }
         std::vector<std::string> st;
+        std::string valid;  // nullable: a node is null if either side is, so the root is valid iff every leaf is
         for (int i = 0; i < pr.n_prog; ++i) {
             const int32_t t = pr.prog[i];
             if (t >= 0 && t < pr.n_leaves) {
                 st.push_back("b" + std::to_string(t));
+                if (g.nul) valid += " & n_b" + std::to_string(t);
             } else {
                 if (st.size() < 2) return false;
                 const std::string r = st.back();
@@ -1217,13 +1274,14 @@ bool emit_pred_typed(TGen &g, const KPred &pr, std::string &body) {
             }
         }
         if (st.size() != 1) return false;
-        body += "    return " + st[0] + ";\n";
+        if (g.nul) body += "    return ((u32)" + st[0] + valid + ") != 0u;\n";
+        else body += "    return " + st[0] + ";\n";
         return true;
     }
     body += "    bool b;\n";
     if (!emit_leaf_typed(g, pr.cmp, pr.cmp_dtype, pr.rhs_operand, pr.lhs, "c.rhs", "p", pr.rhs_col, body, "b"))
         return false;
-    body += "    return b;\n";
+    body += g.nul ? "    return ((u32)b & n_b) != 0u;\n" : "    return b;\n";
     return true;
 }
 
@@ -1244,16 +1302,49 @@ void gen_typed_loop(const Launch &L, std::string &src) {
         return o;
     };
     const std::string S8 = std::to_string(std::max(1, 8 / K));  // scalar loads per lane per column in flight
+    // Nullable scans (all "" otherwise).  NFOR: over the columns with a bitmap vb@.  A group's
+    // rows are bits [r0, r0 + G) of each: the aligned word w@ holding bit r0 and, only when the
+    // groups cross words (`cross`: head is no multiple of G), the next one x@ -- raw words stay
+    // in flight with the column pieces, fq_vbits shifts them into m@ where the rows are evaluated.
+    // EB / GB: the validity arguments of fq_acc for row `i` of the element path (0 where `cond`
+    // fails: no word past the column's is read) and for row r of a group.
+    const bool nul = L.nullable;
+    auto NFOR = [K, nul, &L](const std::string &t) {
+        std::string o;
+        for (int j = 0; nul && j < K; ++j) {
+            if (!L.has_bm[j]) continue;
+            std::string u = t;
+            for (size_t p = 0; (p = u.find('@', p)) != std::string::npos;) u.replace(p, 1, std::to_string(j));
+            o += u;
+        }
+        return o;
+    };
+    auto EB = [K, nul, &L](const std::string &i, const std::string &cond = "") {
+        std::string o;
+        for (int j = 0; nul && j < K; ++j) {
+            const std::string bit = "(u32)((vb" + std::to_string(j) + "[" + i + " >> 6] >> (" + i + " & 63)) & 1ull)";
+            o += !L.has_bm[j] ? ", 1u" : cond.empty() ? ", " + bit : ", (" + cond + " ? " + bit + " : 0u)";
+        }
+        return o;
+    };
+    auto GB = [K, nul, &L]() {
+        std::string o;
+        for (int j = 0; nul && j < K; ++j) o += L.has_bm[j] ? ", (m" + std::to_string(j) + " >> r) & 1u" : ", 1u";
+        return o;
+    };
+    auto VLOAD = [&NFOR](const std::string &ind, const std::string &w, const std::string &x, const std::string &r0) {
+        return NFOR(ind + "fq_vload(vb@, " + r0 + ", cross, " + w + ", " + x + ");\n");
+    };
     // LOAD(dst, pointer, group): the lane's pieces of every column
     auto LOAD = [&FOR](const std::string &ind, const std::string &dst, const std::string &ptr, const std::string &gi) {
         return FOR(ind + "_Pragma(\"unroll\") for (int q = 0; q < NP@; ++q) " + dst + "[q] = __builtin_nontemporal_load(" +
                    ptr + "@ + (" + gi + ") * NP@ + q);\n");
     };
     // ROWS(raw, first row, live): the group's rows through fq_acc
-    auto ROWS = [&FOR](const std::string &ind, const std::string &raw, const std::string &i0, const std::string &live,
+    auto ROWS = [&FOR, &GB](const std::string &ind, const std::string &raw, const std::string &i0, const std::string &live,
                        const char *any) {
         return FOR(ind + "TIn@ y@[G];\n" + ind + "__builtin_memcpy(&y@[0], &" + raw + "[0], G * sizeof(TIn@));\n") + ind +
-               "_Pragma(\"unroll\") for (int r = 0; r < G; ++r) " + any + "fq_acc(acc, " + FOR("y@[r]", ", ") + ", " + i0 +
+               "_Pragma(\"unroll\") for (int r = 0; r < G; ++r) " + any + "fq_acc(acc, " + FOR("y@[r]", ", ") + GB() + ", " + i0 +
                " + r, " + live + ", c, bitmap);\n";
     };
     if (!L.block_mode) {
@@ -1262,32 +1353,40 @@ void gen_typed_loop(const Launch &L, std::string &src) {
                "    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;\n"
                "    if (head >= 0) {\n"
                "    const long long ngrp = (n - head) / G;\n";
+        if (nul) src += "    const bool cross = (head % G) != 0;\n";
         src += FOR("    const P@ *__restrict__ pp@ = (const P@ *)(col@ + head);\n");
         src += "    const long long ntiles = ngrp / 256;\n";
         if (L.prefetch) {
             src += "    // next tile's loads in flight while this tile is evaluated\n";
-            src += FOR("    P@ nxt@[NP@];\n");
+            src += FOR("    P@ nxt@[NP@];\n") + NFOR("    u64 nw@ = 0ull, nx@ = 0ull;\n");
             src += "    if ((long long)blockIdx.x < ntiles) {\n" +
-                   LOAD("        ", "nxt@", "pp", "(long long)blockIdx.x * 256 + threadIdx.x") + "    }\n";
+                   LOAD("        ", "nxt@", "pp", "(long long)blockIdx.x * 256 + threadIdx.x") +
+                   VLOAD("        ", "nw@", "nx@", "head + ((long long)blockIdx.x * 256 + threadIdx.x) * G") + "    }\n";
             src += "    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {\n"
                    "        const long long gi = t * 256 + threadIdx.x;\n";
             src += FOR("        P@ raw@[NP@];\n        _Pragma(\"unroll\") for (int q = 0; q < NP@; ++q) raw@[q] = nxt@[q];\n");
+            src += NFOR("        const u32 m@ = fq_vbits(nw@, nx@, head + gi * G);\n");
             src += "        const long long tn = t + gridDim.x;\n        if (tn < ntiles) {\n" +
-                   LOAD("            ", "nxt@", "pp", "tn * 256 + threadIdx.x") + "        }\n";
+                   LOAD("            ", "nxt@", "pp", "tn * 256 + threadIdx.x") +
+                   VLOAD("            ", "nw@", "nx@", "head + (tn * 256 + threadIdx.x) * G") + "        }\n";
         } else {
             src += "    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {\n"
                    "        const long long gi = t * 256 + threadIdx.x;\n";
             src += FOR("        P@ raw@[NP@];\n") + LOAD("        ", "raw@", "pp", "gi");
+            src += NFOR("        u64 w@, x@;\n") + VLOAD("        ", "w@", "x@", "head + gi * G") +
+                   NFOR("        const u32 m@ = fq_vbits(w@, x@, head + gi * G);\n");
         }
         src += ROWS("        ", "raw@", "head + gi * G", "1u", "") + "    }\n";
         src += "    for (long long gi = ntiles * 256 + g; gi < ngrp; gi += T) {\n";
         src += FOR("        P@ raw@[NP@];\n") + LOAD("        ", "raw@", "pp", "gi");
+        src += NFOR("        u64 w@, x@;\n") + VLOAD("        ", "w@", "x@", "head + gi * G") +
+               NFOR("        const u32 m@ = fq_vbits(w@, x@, head + gi * G);\n");
         src += ROWS("        ", "raw@", "head + gi * G", "1u", "") + "    }\n";
         src += "    const long long tail0 = head + ngrp * G;\n"
                "    const long long nedge = head + (n - tail0);\n"
                "    for (long long t = g; t < nedge; t += T) {\n"
                "        const long long i = t < head ? t : tail0 + (t - head);\n"
-               "        fq_acc(acc, " + FOR("col@[i]", ", ") + ", i, 1u, c, bitmap);\n"
+               "        fq_acc(acc, " + FOR("col@[i]", ", ") + EB("i") + ", i, 1u, c, bitmap);\n"
                "    }\n"
                "    } else {\n"
                "    for (long long i = g; i < n; i += T * " + S8 + ") {\n";
@@ -1297,7 +1396,7 @@ void gen_typed_loop(const Launch &L, std::string &src) {
         src += FOR("            y@[k] = ik < n ? __builtin_nontemporal_load(col@ + ik) : TIn@(0);\n");
         src += "        }\n#pragma unroll\n        for (int k = 0; k < " + S8 + "; ++k) {\n"
                "            const long long ik = i + (long long)k * T;\n"
-               "            fq_acc(acc, " + FOR("y@[k]", ", ") + ", ik, ik < n ? 1u : 0u, c, bitmap);\n"
+               "            fq_acc(acc, " + FOR("y@[k]", ", ") + EB("ik", "ik < n") + ", ik, ik < n ? 1u : 0u, c, bitmap);\n"
                "        }\n    }\n    }\n";
         return;
     }
@@ -1315,20 +1414,24 @@ void gen_typed_loop(const Launch &L, std::string &src) {
            "            const long long ng = (e - s) / G;\n";
     src += FOR("            const P@ *__restrict__ bp@ = (const P@ *)(col@ + s);\n");
     src += "            for (long long v = lane; v < ng; v += 64 * BM_U) {\n";
-    src += FOR("                P@ raw@[BM_U][NP@];\n");
+    src += FOR("                P@ raw@[BM_U][NP@];\n") + NFOR("                u64 w@[BM_U];\n");
     src += "#pragma unroll\n                for (int k = 0; k < BM_U; ++k) {\n"
            "                    const long long vk = v + (long long)k * 64;\n"
            "                    if (vk < ng) {\n" + LOAD("                        ", "raw@[k]", "bp", "vk") +
+           NFOR("                        w@[k] = vb@[(s + vk * G) >> 6];\n") +
            "                    } else {\n" +
            FOR("                        _Pragma(\"unroll\") for (int q = 0; q < NP@; ++q) raw@[k][q] = P@{};\n") +
+           NFOR("                        w@[k] = 0ull;\n") +
            "                    }\n                }\n"
            "#pragma unroll\n                for (int k = 0; k < BM_U; ++k) {\n"
            "                    const long long vk = v + (long long)k * 64;\n"
            "                    const u32 li = vk < ng ? 1u : 0u;\n" +
+           // a block starts on the group's grid here: a group never crosses a word
+           NFOR("                    const u32 m@ = fq_vbits(w@[k], 0ull, s + vk * G);\n") +
            ROWS("                    ", "raw@[k]", "s + vk * G", "li", "any |= ") +
            "                }\n            }\n"
            "            for (long long i = s + ng * G + lane; i < e; i += 64)\n"
-           "                any |= fq_acc(acc, " + FOR("col@[i]", ", ") + ", i, 1u, c, bitmap);\n"
+           "                any |= fq_acc(acc, " + FOR("col@[i]", ", ") + EB("i") + ", i, 1u, c, bitmap);\n"
            "            if (__ballot(any != 0) == 0ull) acc.flags |= " + std::to_string(FQ_STATE_ANY_EMPTY) + "u;\n"
            "            continue;\n        }\n"
            "        for (long long i = s + lane; i < e; i += 64 * " + S8 + ") {\n";
@@ -1338,7 +1441,8 @@ void gen_typed_loop(const Launch &L, std::string &src) {
     src += FOR("                y@[k] = ik < e ? __builtin_nontemporal_load(col@ + ik) : TIn@(0);\n");
     src += "            }\n#pragma unroll\n            for (int k = 0; k < " + S8 + "; ++k) {\n"
            "                const long long ik = i + (long long)k * 64;\n"
-           "                any |= fq_acc(acc, " + FOR("y@[k]", ", ") + ", ik, ik < e ? 1u : 0u, c, bitmap);\n"
+           "                any |= fq_acc(acc, " + FOR("y@[k]", ", ") + EB("ik", "ik < e") +
+           ", ik, ik < e ? 1u : 0u, c, bitmap);\n"
            "            }\n        }\n"
            "        if (__ballot(any != 0) == 0ull) acc.flags |= " + std::to_string(FQ_STATE_ANY_EMPTY) + "u;\n"
            "    }\n";
@@ -1350,21 +1454,31 @@ bool gen_typed_source(const Launch &L, bool chain, std::string &src) {
     const char *V = tname(L.vdtype);
     if (K < 1 || K > FQ_MAX_SCAN_COLS || !V || L.group < 1) return false;
     TGen g;
-    std::string XP, XA;
+    // nullable scans: NP / NA, the rows' validity bits n0 .. n{K-1} after the rows' values
+    const bool nul = L.nullable;
+    g.nul = nul;
+    std::string XP, XA, NP, NA;
     int sum = 0;
     for (int j = 0; j < K; ++j) {
         if (!tname(L.cdt[j])) return false;
         g.cdt[j] = L.cdt[j];
+        g.has_bm[j] = nul && L.has_bm[j];
         sum += fqc::dtype_size(L.cdt[j]);
         const std::string J = std::to_string(j);
         XP += (j ? ", TIn" : "TIn") + J + " x" + J;
         XA += (j ? ", x" : "x") + J;
+        if (nul) NP += ", u32 n" + J, NA += ", n" + J;
     }
     const int32_t pk = L.pred.kind;
     const bool expr_pred = pk == FQ_PRED_EXPR || pk == FQ_PRED_TREE;
     std::string pred_body, val_body;
     if (expr_pred && !emit_pred_typed(g, L.pred, pred_body)) return false;
-    if (chain) {
+    if (nul) {
+        TVal cur = g.X(0);
+        if (chain && !emit_prog_typed(g, val_body, L.val, "v", cur)) return false;
+        cur = ncast(g, val_body, cur, L.vdtype);
+        val_body += "    ok = " + (cur.v.empty() ? std::string("1u") : cur.v) + ";\n    return " + cur.e + ";\n";
+    } else if (chain) {
         TVal cur = g.X(0);
         if (!emit_prog_typed(g, val_body, L.val, "v", cur)) return false;
         val_body += "    return " + tcast(cur, L.vdtype) + ";\n";
@@ -1374,6 +1488,20 @@ bool gen_typed_source(const Launch &L, bool chain, std::string &src) {
 
     src = kTypedCommon;
     src += "#define G " + std::to_string(L.group) + "\n";
+    if (nul)
+        src += R"(struct PartialN { Partial p; u64 valid, reserved; };
+// the aligned bitmap word holding bit r0 and, where groups cross words, the next
+__device__ __forceinline__ void fq_vload(const u64 *__restrict__ vb, long long r0, bool cross, u64 &w, u64 &x) {
+    w = vb[r0 >> 6];
+    x = 0ull;
+    if (cross && (int)(r0 & 63) + G > 64) x = vb[(r0 >> 6) + 1];
+}
+// bits [r0, r0 + G) of the two words
+__device__ __forceinline__ u32 fq_vbits(u64 w, u64 x, long long r0) {
+    const int sh = (int)(r0 & 63);
+    return (u32)((w >> sh) | ((x << 1) << (63 - sh)));
+}
+)";
     for (int j = 0; j < K; ++j) {
         const std::string J = std::to_string(j);
         const int B = L.group * fqc::dtype_size(L.cdt[j]);  // bytes of a lane's piece
@@ -1385,46 +1513,50 @@ bool gen_typed_source(const Launch &L, bool chain, std::string &src) {
     src += "struct Step { u64 c, m, s; };\nstruct Consts { u64 rhs; Step p[" + std::to_string(kSteps) +
            "], v[" + std::to_string(kSteps) + "]; u64 rl[" + std::to_string(FQ_MAX_PRED_LEAVES) + "]; Step pl[" +
            std::to_string(FQ_MAX_PRED_LEAVES) + "][" + std::to_string(kSteps) + "]; };\n";
-    src += "__device__ __forceinline__ bool fq_pred(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n";
+    src += "__device__ __forceinline__ bool fq_pred(" + XP + NP + ", const Consts &c, u32 &flags, u32 live) {\n";
     src += expr_pred ? pred_body : "    return true;\n";
     src += "}\n";
-    src += "__device__ __forceinline__ V fq_val(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n" + val_body + "}\n";
+    src += "__device__ __forceinline__ V fq_val(" + XP + NP + ", const Consts &c, u32 &flags, u32 live" +
+           (nul ? ", u32 &ok" : "") + ") {\n" + val_body + "}\n";
     const uint32_t m = L.mask;
     // block mode: the pieces of BM_U groups in flight, about 128 bytes per lane
     src += "#define BM_U " + std::to_string(std::max(1, 128 / (L.group * sum))) + "\n";
-    src += "struct Acc { V sum, mx, mn; u64 cnt; u32 flags; };\n";
-    src += "__device__ __forceinline__ u32 fq_acc(Acc &acc, " + XP + ", long long idx, u32 live, const Consts &c,\n"
+    src += nul ? "struct Acc { V sum, mx, mn; u64 cnt, val; u32 flags; };\n" : "struct Acc { V sum, mx, mn; u64 cnt; u32 flags; };\n";
+    src += "__device__ __forceinline__ u32 fq_acc(Acc &acc, " + XP + NP + ", long long idx, u32 live, const Consts &c,\n"
            "                                      const u64 *__restrict__ bitmap) {\n"
            "    u32 pass = live;\n";
-    if (expr_pred) src += "    pass &= fq_pred(" + XA + ", c, acc.flags, live) ? 1u : 0u;\n";
+    if (expr_pred) src += "    pass &= fq_pred(" + XA + NA + ", c, acc.flags, live) ? 1u : 0u;\n";
     else if (pk == FQ_PRED_BITMAP)
         src += "    if (live) pass &= (u32)((bitmap[idx >> 6] >> (idx & 63)) & 1ull);\n";
-    src += "    (void)idx; (void)bitmap;\n    const V v = fq_val(" + XA + ", c, acc.flags, pass);\n";
-    if (m & FQ_AGG_SUM) src += "    acc.sum = fq_add<V>(acc.sum, pass ? v : V(0));\n";
-    if (m & FQ_AGG_MAX) src += "    acc.mx = pass ? vmax(acc.mx, v) : acc.mx;\n";
-    if (m & FQ_AGG_MIN) src += "    acc.mn = pass ? vmin(acc.mn, v) : acc.mn;\n";
-    src += "    acc.cnt += pass;\n    return pass;\n}\n";
-    src += R"(
-__device__ __forceinline__ Partial wg_reduce(Acc acc) {
+    // N(t): text of the nullable source only
+    auto N = [nul](const char *t) { return std::string(nul ? t : ""); };
+    // sum / max / min (and the block ballot) take the kept rows -- whose value is valid, when there are nulls
+    const std::string take = nul ? "pv" : "pass";
+    src += "    (void)idx; (void)bitmap;\n" + N("    u32 ok;\n") + "    const V v = fq_val(" + XA + NA + ", c, acc.flags, pass" +
+           N(", ok") + ");\n" + N("    const u32 pv = pass & ok;\n");
+    if (m & FQ_AGG_SUM) src += "    acc.sum = fq_add<V>(acc.sum, " + take + " ? v : V(0));\n";
+    if (m & FQ_AGG_MAX) src += "    acc.mx = " + take + " ? vmax(acc.mx, v) : acc.mx;\n";
+    if (m & FQ_AGG_MIN) src += "    acc.mn = " + take + " ? vmin(acc.mn, v) : acc.mn;\n";
+    src += "    acc.cnt += pass;\n" + N("    acc.val += pv;\n") + "    return " + take + ";\n}\n";
+    src += "\n__device__ __forceinline__ Partial" + N("N") + R"( wg_reduce(Acc acc) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         acc.sum = fq_add<V>(acc.sum, shfl(acc.sum, off));
         acc.mx = vmax(acc.mx, shfl(acc.mx, off));
         acc.mn = vmin(acc.mn, shfl(acc.mn, off));
         acc.cnt += shfl(acc.cnt, off);
-        acc.flags |= (u32)__shfl_xor((int)acc.flags, off, 64);
+)" + N("        acc.val += shfl(acc.val, off);\n") + R"(        acc.flags |= (u32)__shfl_xor((int)acc.flags, off, 64);
     }
     __shared__ V s_sum[4], s_mx[4], s_mn[4];
     __shared__ u64 s_cnt[4];
-    __shared__ u32 s_flags[4];
+)" + N("    __shared__ u64 s_val[4];\n") + R"(    __shared__ u32 s_flags[4];
     const int wave = threadIdx.x / 64;
     if ((threadIdx.x & 63) == 0) {
         s_sum[wave] = acc.sum; s_mx[wave] = acc.mx; s_mn[wave] = acc.mn;
         s_cnt[wave] = acc.cnt; s_flags[wave] = acc.flags;
-    }
+)" + N("        s_val[wave] = acc.val;\n") + R"(    }
     __syncthreads();
-    Partial p;
-    if (threadIdx.x == 0) {
+)" + (nul ? "    PartialN pn;\n    Partial &p = pn.p;\n" : "    Partial p;\n") + R"(    if (threadIdx.x == 0) {
         V sum = s_sum[0], mx = s_mx[0], mn = s_mn[0];
         u64 cnt = s_cnt[0];
         u32 flags = s_flags[0];
@@ -1435,20 +1567,22 @@ __device__ __forceinline__ Partial wg_reduce(Acc acc) {
         }
         p.sum = fq_bits<V>(sum); p.max = fq_bits<V>(mx); p.min = fq_bits<V>(mn);
         p.count = cnt; p.blocks = 0; p.flags = flags; p.dtype = )" + std::to_string(L.vdtype) + R"(;
-    }
-    return p;
+)" + N("        pn.valid = s_val[0] + s_val[1] + s_val[2] + s_val[3]; pn.reserved = 0;\n") + R"(    }
+    return )" + (nul ? "pn" : "p") + R"(;
 }
 )";
     std::string cols_params;
     for (int j = 0; j < K; ++j)
         cols_params += (j ? ", const TIn" : "const TIn") + std::to_string(j) + " *__restrict__ col" + std::to_string(j);
+    for (int j = 0; nul && j < K; ++j)  // the bitmaps follow the columns
+        if (L.has_bm[j]) cols_params += ", const u64 *__restrict__ vb" + std::to_string(j);
     src += "extern \"C\" __global__ void __launch_bounds__(256)\n"
            "fq_jit_scan(" + cols_params + ", long long n, long long head, long long R,\n"
-           "            const u64 *__restrict__ bitmap, Consts c, Partial *parts) {\n"
-           "    Acc acc;\n    acc.sum = V(0); acc.mx = fq_max_id<V>(); acc.mn = fq_min_id<V>(); acc.cnt = 0; acc.flags = 0;\n";
+           "            const u64 *__restrict__ bitmap, Consts c, Partial" + N("N") + " *parts) {\n"
+           "    Acc acc;\n    acc.sum = V(0); acc.mx = fq_max_id<V>(); acc.mn = fq_min_id<V>(); acc.cnt = 0; acc.flags = 0;\n" +
+           N("    acc.val = 0;\n");
     gen_typed_loop(L, src);
-    src += R"JIT(
-    const Partial p = wg_reduce(acc);
+    src += "\n    const Partial" + N("N") + R"JIT( p = wg_reduce(acc);
     if (threadIdx.x == 0) parts[blockIdx.x] = p;
 }
 )JIT";
@@ -1460,6 +1594,10 @@ __device__ __forceinline__ Partial wg_reduce(Acc acc) {
 std::string typed_shape_key(const Launch &L, bool chain, int dev) {
     std::string k = "typed";
     auto put = [&k](int32_t v) { k.append(reinterpret_cast<const char *>(&v), sizeof v); };
+    if (L.nullable) {  // a source of its own per set of columns that carry a bitmap
+        k += "nullable";
+        for (int j = 0; j < L.n_cols; ++j) put(L.has_bm[j] ? 1 : 0);
+    }
     put(dev);
     put(L.n_cols);
     for (int j = 0; j < L.n_cols; ++j) put(L.cdt[j]);
@@ -4412,11 +4550,16 @@ fq_status jit_scan(int32_t col_dtype, bool chain, const Launch &L, bool *used, b
     Partial *parts = L.parts;
     if (L.n_cols > 1 || L.typed) {  // fq_jit_scan(col0 .. col{K-1}, n, head, R, ...); head < 0: the element path
         const void *cols[FQ_MAX_SCAN_COLS];
-        void *args[FQ_MAX_SCAN_COLS + 6];
+        const uint64_t *vbs[FQ_MAX_SCAN_COLS];
+        void *args[2 * FQ_MAX_SCAN_COLS + 6];
         int na = 0;
         for (int j = 0; j < L.n_cols; ++j) {
             cols[j] = L.cols[j];
             args[na++] = &cols[j];
+        }
+        for (int j = 0; L.nullable && j < L.n_cols; ++j) {
+            vbs[j] = L.validity[j];
+            if (L.has_bm[j]) args[na++] = &vbs[j];
         }
         if (!L.vec) head = -1;
         args[na++] = &n;

@@ -45,6 +45,12 @@ struct Launch {
     bool typed;
     int group;
     bool prefetch;
+    // fq_aggregate_nullable (a typed launch): has_bm[j], column j carries an Arrow
+    // validity bitmap validity[j] (bit i = row i of cols[j]); the partials behind
+    // `parts` are PartialN
+    bool nullable;
+    bool has_bm[FQ_MAX_SCAN_COLS];
+    const uint64_t *validity[FQ_MAX_SCAN_COLS];
 };
 
 // Row group of a typed scan over columns of the given widths: the largest

@@ -27,7 +27,8 @@ GPU_SYMBOLS = [
     "fq_filter_project_columns_workspace_bytes", "fq_filter_project_columns", "fq_filter_project_blocks_columns",
     "fq_predicate_bitmap_columns", "fq_jit_prepare_project_columns", "fq_aggregate_typed", "fq_jit_prepare_typed",
     "fq_filter_project_typed_workspace_bytes", "fq_filter_project_typed", "fq_filter_project_blocks_typed",
-    "fq_predicate_bitmap_typed", "fq_jit_prepare_project_typed",
+    "fq_predicate_bitmap_typed", "fq_jit_prepare_project_typed", "fq_aggregate_nullable_workspace_bytes",
+    "fq_aggregate_nullable", "fq_jit_prepare_nullable",
 ]
 
 
@@ -76,6 +77,11 @@ _protos = {
                                        C.c_uint32, vp, vp, C.c_size_t, vp]),
     "fq_jit_prepare_typed": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred), P(abi.fq_expr),
                                          C.c_uint32, P(C.c_int32)]),
+    "fq_aggregate_nullable_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "fq_aggregate_nullable": (C.c_int32, [P(abi.fq_col), P(vp), C.c_int32, C.c_int64, P(abi.fq_pred), P(abi.fq_expr),
+                                          C.c_uint32, vp, vp, C.c_size_t, vp]),
+    "fq_jit_prepare_nullable": (C.c_int32, [P(abi.fq_col), P(C.c_uint8), C.c_int32, C.c_int64, P(abi.fq_pred),
+                                            P(abi.fq_expr), C.c_uint32, P(C.c_int32)]),
     "fq_arith_result_type": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, P(C.c_int32)]),
     "fq_arith": (C.c_int32, [C.c_int32, P(abi.fq_col), P(abi.fq_value), P(abi.fq_col),
                              P(abi.fq_value), P(abi.fq_col), vp, vp]),

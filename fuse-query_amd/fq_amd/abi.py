@@ -120,6 +120,15 @@ class fq_group_table(C.Structure):
                 ("dtypes", C.c_int32 * MAX_GROUP_AGGS)]
 
 assert C.sizeof(fq_agg_state) == 48
+
+
+class fq_agg_state_n(C.Structure):
+    """fq_aggregate_nullable's state: s.count = kept rows (nulls included),
+    valid = kept rows whose value is valid (sum/max/min hold a value iff > 0)."""
+    _fields_ = [("s", fq_agg_state), ("valid", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(fq_agg_state_n) == 64
 assert C.sizeof(fq_step) == 24
 
 

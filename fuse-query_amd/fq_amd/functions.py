@@ -45,7 +45,7 @@ FUNCTION_SYMBOLS = [
     "fq_function_display", "fq_function_set_depth", "fq_function_return_type", "fq_function_nullable",
     "fq_function_eval", "fq_function_accumulate", "fq_function_accumulate_result", "fq_function_merge_state",
     "fq_function_merge_result", "fq_data_value_arithmetic_op", "fq_data_value_aggregate_op",
-    "fq_functions_accumulate", "fq_functions_eval",
+    "fq_functions_accumulate", "fq_functions_eval", "fq_functions_accumulate_nullable",
 ]
 
 _protos = {
@@ -62,6 +62,7 @@ _protos = {
                                      P(C.c_int32), P(C.c_int64), P(C.c_int32), P(fq_scalar)]),
     "fq_function_accumulate": (C.c_int32, [OPT, OPT, P(fq_block)]),
     "fq_functions_accumulate": (C.c_int32, [OPT, P(OPT), C.c_int32, P(fq_block)]),
+    "fq_functions_accumulate_nullable": (C.c_int32, [OPT, P(OPT), C.c_int32, P(fq_block), P(C.c_void_p)]),
     "fq_functions_eval": (C.c_int32, [OPT, P(OPT), C.c_int32, P(fq_block), P(C.c_void_p), C.c_size_t, C.c_void_p,
                                       P(C.c_int32), P(C.c_int64), P(C.c_size_t), P(C.c_int32)]),
     "fq_function_accumulate_result": (C.c_int32, [OPT, P(fq_scalar), C.c_size_t, P(C.c_size_t)]),
@@ -257,6 +258,18 @@ class Function:
         _sync_torch()
         arr = (OPT * max(1, len(funcs)))(*[f.h for f in funcs])
         check(lib.fq_functions_accumulate(engine.h, arr, len(funcs), C.byref(block._abi())))
+
+    @staticmethod
+    def accumulate_all_nullable(engine, funcs, block, validity):
+        """accumulate_all over a block of nullable columns through
+        fq_functions_accumulate_nullable.  validity: per column of the block None
+        (every row valid) or a UInt64 ops.DeviceColumn of ceil(len / 64) Arrow
+        validity-bitmap words (bit i = row i of the column is valid)."""
+        _sync_torch()
+        assert len(validity) == len(block.columns)
+        arr = (OPT * max(1, len(funcs)))(*[f.h for f in funcs])
+        vb = (C.c_void_p * max(1, len(validity)))(*[getattr(v, "ptr", v) for v in validity])
+        check(lib.fq_functions_accumulate_nullable(engine.h, arr, len(funcs), C.byref(block._abi()), vb))
 
     @staticmethod
     def eval_all(engine, funcs, block, blocks=False, cap=None):

@@ -231,8 +231,42 @@ def aggregate_typed(cols, block_rows=0, pred=None, value=None, mask=0xF, ws=None
     return state_from_device(aggregate_typed_async(cols, block_rows, pred, value, mask, ws, None, stream))
 
 
+def aggregate_nullable_async(cols, validity, block_rows=0, pred=None, value=None, mask=0xF, ws=None, out=None,
+                             stream=None):
+    """Launch fq_aggregate_nullable: aggregate_typed_async over nullable columns.
+    validity: per column None or a UInt64 DeviceColumn of ceil(len / 64) Arrow
+    validity-bitmap words (bit i = row i of the column is valid); returns the
+    device tensor holding the fq_agg_state_n."""
+    require_gpu()
+    ws = ws or Workspace(lib.fq_aggregate_nullable_workspace_bytes(cols[0].len if cols else 0))
+    if out is None:
+        out = torch.empty(64, dtype=torch.uint8, device="cuda")
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    vb = None
+    if validity is not None:
+        vb = (C.c_void_p * max(len(cols), 1))(*[getattr(v, "ptr", v) for v in validity])
+    check(lib.fq_aggregate_nullable(arr, vb, len(cols), block_rows, C.byref(pred) if pred is not None else None,
+                                    C.byref(value) if value is not None else None, mask,
+                                    C.c_void_p(out.data_ptr()), ws.ptr, ws.nbytes, _stream(stream)))
+    return out
+
+
+def aggregate_nullable(cols, validity, block_rows=0, pred=None, value=None, mask=0xF, ws=None, stream=None):
+    """Fused AggregatePartial over up to abi.MAX_SCAN_COLS nullable columns of
+    one device block -> host fq_agg_state_n."""
+    t = aggregate_nullable_async(cols, validity, block_rows, pred, value, mask, ws, None, stream)
+    return abi.fq_agg_state_n.from_buffer_copy(t.cpu().numpy().tobytes())
+
+
 def state_values(st):
-    """fq_agg_state -> dict(sum, max, min, count, blocks, flags) of Python values."""
+    """fq_agg_state -> dict(sum, max, min, count, blocks, flags) of Python values;
+    fq_agg_state_n: also `valid`, and sum / max / min are None when valid == 0."""
+    if isinstance(st, abi.fq_agg_state_n):
+        d = state_values(st.s)
+        d["valid"] = st.valid
+        if st.valid == 0:
+            d["sum"] = d["max"] = d["min"] = None
+        return d
     dt = st.dtype
     return {
         "sum": from_bits(st.sum, dt), "max": from_bits(st.max, dt),
@@ -616,6 +650,22 @@ def jit_prepare_typed(dtypes, pred=None, value=None, mask=abi.AGG_SUM, block_row
     out = C.c_int32(0)
     check(lib.fq_jit_prepare_typed(arr, len(dtypes), int(block_rows), C.byref(pred) if pred is not None else None,
                                    C.byref(value) if value is not None else None, mask, C.byref(out)))
+    return bool(out.value)
+
+
+def jit_prepare_nullable(dtypes, has_validity=None, pred=None, value=None, mask=abi.AGG_SUM, block_rows=0,
+                         length=1 << 30, lengths=None):
+    """jit_prepare for fq_aggregate_nullable: one dtype per column, and whether it
+    will carry a validity bitmap (default: none does)."""
+    lens = list(lengths) if lengths is not None else [int(length)] * len(dtypes)
+    arr = (abi.fq_col * max(len(dtypes), 1))(*[abi.fq_col(None, int(n), dt, 0) for dt, n in zip(dtypes, lens)])
+    hv = None
+    if has_validity is not None:
+        hv = (C.c_uint8 * max(len(dtypes), 1))(*[1 if h else 0 for h in has_validity])
+    out = C.c_int32(0)
+    check(lib.fq_jit_prepare_nullable(arr, hv, len(dtypes), int(block_rows),
+                                      C.byref(pred) if pred is not None else None,
+                                      C.byref(value) if value is not None else None, mask, C.byref(out)))
     return bool(out.value)
 
 

@@ -317,6 +317,24 @@ fq_status fq_function_accumulate(fq_engine *e, fq_function *f, const fq_block *b
  * first failing function's error is returned (the reference's `?`); the
  * functions before it have accumulated.  Complete when the call returns.   */
 fq_status fq_functions_accumulate(fq_engine *e, fq_function *const *fs, int32_t n, const fq_block *b);
+/* The same over a block of nullable columns.  validity[i] belongs to
+ * b->columns[i]: NULL (every row valid) or a device Arrow validity bitmap as
+ * fq_aggregate_nullable takes it (8-byte aligned, ceil(len / 64) words, bit 0 =
+ * row 0 of the column; a bit offset is the host's to re-base).  The array
+ * itself must be non-NULL; all entries may be NULL: then only casts make nulls,
+ * and the call has the reference's cast behaviour (an overflowing cast is a
+ * null), not the FQ_E_UNSUPPORTED "cast produced nulls" of
+ * fq_functions_accumulate.  Every (argument, filter) is one
+ * fq_aggregate_nullable scan of up to FQ_MAX_SCAN_COLS columns (the filter's
+ * first, then the argument's) and the states replay the reference's per-block
+ * state machine: Count adds the kept rows, nulls included; Min / Max / Sum see
+ * None for a block without a valid kept value (a Sum over >= 2 blocks then
+ * fails with "DataValue to array cannot be NONE NULL").  A statement that does
+ * not fuse -- a fifth column, the hipRTC kernels off, a non-numeric column, an
+ * expression past the step budget -- fails with FQ_E_UNSUPPORTED and a message
+ * naming the reason: there is no unfused path over nulls.                   */
+fq_status fq_functions_accumulate_nullable(fq_engine *e, fq_function *const *fs, int32_t n, const fq_block *b,
+                                           const uint64_t *const *validity);
 /* ProjectionTransform's loop body for one block
  * (transform_projection.rs:45-56: `for func in funcs {
  * func.eval(&block)?.to_array(block.num_rows()) }`) over n handles at once,

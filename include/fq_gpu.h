@@ -304,6 +304,52 @@ fq_status fq_jit_prepare_typed(const fq_col *cols, int32_t n_cols, int64_t block
                                const fq_pred *pred, const fq_expr *value, uint32_t agg_mask,
                                int32_t *specialised);
 
+/* ---- The same scan over nullable columns (Arrow validity bitmaps) ----
+ * validity[j] belongs to cols[j]: NULL (every row valid) or a device pointer,
+ * 8-byte aligned (FQ_E_INVALID otherwise), to ceil(len / 64) u64 words whose
+ * bit i (LSB first, as Boolean columns are laid out) is 1 when row i of
+ * cols[j].data is valid.  Bit 0 is row 0 of cols[j].data: a sliced array whose
+ * bitmap has a bit offset is the host's to re-base.  Bits at and past len are
+ * ignored and no word past ceil(len / 64) is read.  `validity` itself must be
+ * non-NULL.  A value under a 0 bit never influences a result, a flag or an
+ * error.  The rules are arrow 2.0's as the reference uses them:
+ *   - a constant is valid; a step is valid iff both operands are; a cast is
+ *     valid iff its input is and the value is in range -- an out-of-range cast
+ *     is a null here, FQ_STATE_CAST_NULL is never set;
+ *   - FQ_STATE_DIV_ZERO: a zero divisor on a live row whose operands are both
+ *     valid (predicate: any row; value: kept rows);
+ *   - a comparison is null if either side is; an and / or node is null if
+ *     either side is (arrow 2.0 combines the null bitmaps: `true or null` is
+ *     null); a row is kept iff the predicate is valid and true.  An
+ *     FQ_PRED_BITMAP predicate has no validity of its own;
+ *   - count = kept rows, nulls included; valid = kept rows whose value is
+ *     valid; sum / max / min fold those and hold a value iff valid > 0 (no scan
+ *     runs for a request of count alone without predicate and expression:
+ *     valid is then 0);
+ *   - FQ_STATE_ANY_EMPTY: some reference block had no valid kept value, with
+ *     or without a predicate (reported, as by the other entry points, when
+ *     agg_mask has FQ_AGG_SUM or the scan covers a single reference block).
+ * Arguments, coercion checks, block_rows, predicate kinds and the fixed-order
+ * fold are fq_aggregate_typed's.  This entry point always runs the typed
+ * hipRTC kernels, 64-bit shapes included (FQ_E_UNSUPPORTED with FQ_JIT_OFF or
+ * without hipRTC); a column without a bitmap costs no bitmap load.  The
+ * workspace holds 64-byte partials: fq_aggregate_nullable_workspace_bytes.
+ * fq_jit_prepare_nullable: has_validity[j] != 0 where the call will pass a
+ * bitmap (NULL: none).                                                       */
+typedef struct fq_agg_state_n {   /* 64 bytes */
+    fq_agg_state s;               /* count = rows kept by the predicate (nulls included) */
+    uint64_t valid;               /* kept rows whose value is valid: sum/max/min hold a value iff valid > 0 */
+    uint64_t reserved;
+} fq_agg_state_n;
+size_t fq_aggregate_nullable_workspace_bytes(int64_t len);
+fq_status fq_aggregate_nullable(const fq_col *cols, const uint64_t *const *validity, int32_t n_cols,
+                                int64_t block_rows, const fq_pred *pred, const fq_expr *value,
+                                uint32_t agg_mask, fq_agg_state_n *d_out, void *d_ws, size_t ws_bytes,
+                                void *stream);
+fq_status fq_jit_prepare_nullable(const fq_col *cols, const uint8_t *has_validity, int32_t n_cols,
+                                  int64_t block_rows, const fq_pred *pred, const fq_expr *value,
+                                  uint32_t agg_mask, int32_t *specialised);
+
 /* ---- ArithmeticFunction::eval (data_array_arithmetic.rs:14-55) ----
  * Exactly one of {lhs, lhs_scalar} and one of {rhs, rhs_scalar} is non-NULL.
  * out->data must hold out->len elements of the coercion type returned by

@@ -12,6 +12,7 @@ usage: python tools/bench_kernels.py [--rows 1.25e9] [--reps 10] > gpurun_out/ke
        python tools/bench_kernels.py --only pcols [--q6-rows 134217728] [--reps 20]   (Filter -> Projection over 3 columns)
        python tools/bench_kernels.py --only typed [--q6-rows 134217728] [--reps 20]   (the Q6 shape over narrow columns)
        python tools/bench_kernels.py --only ptyped [--q6-rows 134217728] [--reps 20]   (Filter -> Projection over them)
+       python tools/bench_kernels.py --only nullable [--q6-rows 134217728] [--reps 20]   (the Q6 shape with validity bitmaps)
 """
 import argparse
 import ctypes as C
@@ -540,18 +541,111 @@ def ptyped_lines(n, reps, st, res):
         "typed_below_widened": {"block_stream": bool(med(t_blk) < med(w_blk)), "contiguous": bool(med(t_con) < med(w_con))}}})
 
 
+def nullable_lines(n, reps, st, res):
+    """The Q6 statement of typed_lines (17 B/row, about 3/8 of the rows kept) with Arrow validity bitmaps,
+    flat and in block mode, in ONE process: (1) fq_aggregate_typed without bitmaps, the yardstick; then
+    fq_aggregate_nullable with (2) four bitmaps of all ones, (3) four bitmaps with 10 % seeded random nulls
+    each, (4) a bitmap on quantity alone (all ones).  Algorithmic bytes: 17 B + 1/8 B per bitmap per row.
+    Every launch event-timed; each leg's ratio is its median over leg 1's median."""
+    from fq_amd.expr import Col, chain_columns, load, pred_tree_columns
+    F64, F32, I32, U8, U64 = abi.DT_FLOAT64, abi.DT_FLOAT32, abi.DT_INT32, abi.DT_UINT8, abi.DT_UINT64
+    K, Q = 9950, 26
+    g = torch.Generator(device="cuda")
+    g.manual_seed(9)  # typed_lines' generator
+    t_price = torch.rand(n, dtype=torch.float64, device="cuda", generator=g) * 999.0 + 1.0
+    t_disc = torch.randint(0, 11, (n,), device="cuda", generator=g).to(torch.float32) / 100.0
+    t_ship = torch.randint(8000, 10600, (n,), dtype=torch.int32, device="cuda", generator=g)
+    t_qty = torch.randint(1, 51, (n,), dtype=torch.uint8, device="cuda", generator=g)
+    cols = [ops.DeviceColumn(t.view(torch.uint8), n, dt) for t, dt in zip((t_price, t_disc, t_ship, t_qty), (F64, F32, I32, U8))]
+    dts = [F64, F32, I32, U8]
+    pred = pred_tree_columns(dts, [([load(2)], "<", (K, "Int32")), ([load(3)], "<", (Q, "UInt8"))], [0, 1, "and"])
+    value, vdt = chain_columns(dts, [("*", Col(1))])
+    assert vdt == F64
+    words = (n + 63) // 64
+    ones = torch.full((words,), -1, dtype=torch.int64, device="cuda")
+    valid, bitmaps = [], []
+    for j in range(4):  # 10 % nulls per column, seeded; packed LSB-first into u64 words
+        v = torch.rand(words * 64, device="cuda", generator=g) >= 0.1
+        w = (v.view(words, 64).to(torch.int64) << torch.arange(64, device="cuda", dtype=torch.int64)).sum(dim=1)
+        valid.append(v[:n])
+        bitmaps.append(w)
+    ccols = (abi.fq_col * 4)(*[c.col() for c in cols])
+    aws = ops.Workspace(lib.fq_aggregate_workspace_bytes(n))
+    nws = ops.Workspace(lib.fq_aggregate_nullable_workspace_bytes(n))
+    dst = torch.empty(64, dtype=torch.uint8, device="cuda")
+    SC = abi.AGG_SUM | abi.AGG_COUNT
+
+    def vb(ptrs):
+        return (C.c_void_p * 4)(*ptrs)
+
+    legs = [("2 four bitmaps, all ones", vb([ones.data_ptr()] * 4), 4, None),
+            ("3 four bitmaps, 10 % nulls each", vb([b.data_ptr() for b in bitmaps]), 4, valid),
+            ("4 quantity's bitmap alone, all ones", vb([None, None, None, ones.data_ptr()]), 1, None)]
+
+    def expected(v):
+        keep = (t_ship < K) & (t_qty < Q)
+        ok = keep
+        if v is not None:
+            keep = keep & v[2] & v[3]
+            ok = keep & v[0] & v[1]
+        prod = t_price[ok] * t_disc[ok].to(torch.float64)
+        return int(keep.sum()), int(ok.sum()), float(prod.sum()), float(prod.abs().sum())
+
+    def typed(br):
+        check(lib.fq_aggregate_typed(ccols, 4, br, C.byref(pred), C.byref(value), SC, C.c_void_p(dst.data_ptr()),
+                                     aws.ptr, aws.nbytes, st))
+
+    def nullable(ptrs, br):
+        check(lib.fq_aggregate_nullable(ccols, ptrs, 4, br, C.byref(pred), C.byref(value), SC,
+                                        C.c_void_p(dst.data_ptr()), nws.ptr, nws.nbytes, st))
+
+    def rec(name, ts, nbytes, note=""):
+        ms = statistics.median(ts)
+        gbps = nbytes / (ms * 1e-3) / 1e9
+        res.append({"kernel": name, "ms": ms, "ms_min": min(ts), "ms_max": max(ts), "reps": len(ts),
+                    "algorithmic_bytes": nbytes, "achieved_gbps": gbps, "frac_of_peak": gbps / PEAK, "note": note})
+        print("%-58s %8.3f ms [%.3f .. %.3f]  %7.0f GB/s  %4.1f %%" % (name, ms, min(ts), max(ts), gbps,
+                                                                     100 * gbps / PEAK), file=sys.stderr)
+        return ts
+
+    summary = {}
+    for mode, br in (("flat", 0), ("block_mode", 10000)):
+        t1 = rec("nullable q6 %s: 1 fq_aggregate_typed, no bitmaps" % mode, timed_all(lambda: typed(br), reps), 17 * n,
+                 "the typed scan of the same statement: the yardstick of the legs below")
+        kept, _, want, scale = expected(None)
+        got = ops.state_from_device(dst[:48])
+        assert got.count == kept and abs(ops.state_values(got)["sum"] - want) <= 1e-12 * scale
+        out = {"typed_ms": statistics.median(t1), "typed_ms_min": min(t1), "typed_ms_max": max(t1)}
+        for name, ptrs, nb, v in legs:
+            nbytes = 17 * n + nb * ((n + 7) // 8)
+            ts = rec("nullable q6 %s: %s" % (mode, name), timed_all(lambda: nullable(ptrs, br), reps), nbytes,
+                     "fq_aggregate_nullable, %.3f B/row" % (nbytes / n))
+            sn = abi.fq_agg_state_n.from_buffer_copy(dst.cpu().numpy().tobytes())
+            kept, ok, want, scale = expected(v)
+            assert sn.s.count == kept and sn.valid == ok and not sn.s.flags & 6, (name, sn.s.count, kept, sn.valid, ok)
+            assert abs(ops.state_values(sn)["sum"] - want) <= 1e-12 * scale, (name, ops.state_values(sn)["sum"], want)
+            out["leg" + name[0]] = {"ms": statistics.median(ts), "over_typed": statistics.median(ts) / statistics.median(t1),
+                                    "bytes_over_typed": nbytes / (17 * n), "tb_per_s": nbytes / (statistics.median(ts) * 1e-3) / 1e12,
+                                    "share_of_8_tb_per_s": nbytes / (statistics.median(ts) * 1e-3) / 1e9 / PEAK,
+                                    "above_bytes_by_more_than_typed_spread": bool(
+                                        statistics.median(ts) - statistics.median(t1) * nbytes / (17 * n) > max(t1) - min(t1))}
+        summary[mode] = out
+    res.append({"nullable_q6": {"rows": n, **summary}})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=float, default=1.25e9)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--only", choices=["q6", "pcols", "typed", "ptyped"], default=None, help="run only the named group of lines")
+    ap.add_argument("--only", choices=["q6", "pcols", "typed", "ptyped", "nullable"], default=None, help="run only the named group of lines")
     ap.add_argument("--q6-rows", type=float, default=float(1 << 27))
     args = ap.parse_args()
     n = int(args.rows)
     st = ops._stream()
     res = []
-    if args.only in ("q6", "pcols", "typed", "ptyped"):
-        {"q6": q6_lines, "pcols": pcols_lines, "typed": typed_lines, "ptyped": ptyped_lines}[args.only](
+    if args.only in ("q6", "pcols", "typed", "ptyped", "nullable"):
+        {"q6": q6_lines, "pcols": pcols_lines, "typed": typed_lines, "ptyped": ptyped_lines,
+         "nullable": nullable_lines}[args.only](
             int(args.q6_rows), args.reps, st, res)
         print(json.dumps({"rows": int(args.q6_rows), "peak_gbps": PEAK, "device": torch.cuda.get_device_name(0),
                           "kernels": res}, indent=1))

@@ -15,7 +15,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADERS = ("fq_gpu.h", "fq_engine.h", "fq_comm.h")
-SCALARS = {"int32_t": "i32", "int64_t": "i64", "uint32_t": "u32", "uint64_t": "u64", "size_t": "usize",
+SCALARS = {"uint8_t": "u8", "int32_t": "i32", "int64_t": "i64", "uint32_t": "u32", "uint64_t": "u64", "size_t": "usize",
            "fq_status": "fq_status", "char": "c_char", "void": "c_void", "double": "f64",
            "fq_allreduce_fn": "fq_allreduce_fn"}
 RUST_KEYWORDS = {"in": "input", "type": "ty", "ref": "r#ref", "fn": "f", "mod": "m"}

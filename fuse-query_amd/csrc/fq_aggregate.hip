@@ -504,6 +504,9 @@ static fq_status lower_expr_impl(const fq_expr &e, const int32_t *cdt, int n_col
             acc = cdt[c];
             continue;
         }
+        // a one-column *_columns / *_typed call is the single-column entry point: its FQ_OP_LOAD names the
+        // one column (the caller checked the index), which acc already is
+        if (st.op == FQ_OP_LOAD && i == 0) continue;
         if (st.op == FQ_OP_PUSH) {  // expression tree: acc onto the stack, restart from the column
             if (depth >= FQ_MAX_STACK) return fqc::fail(FQ_E_UNSUPPORTED, "expression tree too deep for the fused device path");
             if (!typed && !is_chain_dtype(col_dtype))

@@ -88,6 +88,16 @@ def test_all_64_bit_shapes_generate_the_columns_source(i, tmp_path):
         assert "fq_cast<" not in new[0]  # the 64-bit text, not the typed one
 
 
+def test_one_64_bit_column_accepts_a_load_of_its_one_column():
+    # FQ_OP_LOAD over one 64-bit column: the single-column module, whose lowering refused the step as "bad op"
+    for dt, k in ((I64, (3, "Int64")), (U64, 3), (F64, 2.0)):
+        pred = predicate_columns([dt], [load(0), ("+", k)], "<", Col(0))
+        values = [chain_columns([dt], [load(0), ("%", k)])[0], chain_columns([dt], [load(0)])[0], None]
+        for fn in (ops.jit_prepare_project_columns, ops.jit_prepare_project_typed):
+            for br in (0, 10000):
+                assert fn([dt], pred=pred, values=values, block_rows=br)
+
+
 # ---------------------------------------------------------------------------
 # narrow and mixed-width shapes compile
 # ---------------------------------------------------------------------------

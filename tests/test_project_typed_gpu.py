@@ -520,3 +520,16 @@ def test_all_64_bit_call_is_the_columns_call():
         assert np.array_equal(g.to_numpy(), w.to_numpy())
     assert np.array_equal(ops.predicate_bitmap_typed(cols, pred).to_numpy(),
                           ops.predicate_bitmap_columns(cols, pred).to_numpy())
+
+
+def test_one_64_bit_column_with_a_load_of_its_one_column():
+    # load(0) over one 64-bit column (the single-column module): the outputs of the program without it
+    n = 30017
+    x = np.random.default_rng(47).integers(-(1 << 40), 1 << 40, n).astype(np.int64)
+    dts = [I64]
+    case = Case(["x"], dts, [x], predicate_columns(dts, [load(0), ("%", (8, "Int64"))], "<", (3, "Int64")),
+                [chain_columns(dts, [load(0), ("+", Col(0))])[0], chain_columns(dts, [load(0)])[0], None],
+                R.Compare("<", R.Arith("%", fld("x"), const(8, "Int64")), const(3, "Int64")),
+                [R.Arith("+", fld("x"), fld("x")), fld("x"), fld("x")])
+    for layout in ("aligned", "all_offset"):
+        every_entry_point(case, layout)

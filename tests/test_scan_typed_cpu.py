@@ -182,6 +182,22 @@ def test_all_64_bit_shapes_generate_byte_identical_sources(i, tmp_path):
         assert texts[0] == texts[1] and compiled[0] == sum(reports[0])  # an identity scan is precompiled: no dump
 
 
+def test_one_64_bit_column_accepts_a_load_of_its_one_column():
+    """include/fq_gpu.h: FQ_OP_LOAD is a step of the *_columns calls, and with n_cols == 1 such a call is the
+    single-column entry point.  load(0) over one column was refused there as "fq_step: bad op" (found by
+    tests/test_fuzz_typed_cpu.py); a column that is not there still is a bad index."""
+    for dt, k in ((I64, (3, "Int64")), (U64, 3), (F64, 2.0)):
+        pred = predicate_columns([dt], [load(0), ("+", k)], "<", Col(0))
+        for steps in ([load(0), ("%", k)], [load(0)]):
+            value = chain_columns([dt], steps)[0]
+            for fn in (ops.jit_prepare_columns, ops.jit_prepare_typed):
+                for br in (0, 10000):
+                    assert fn([dt], pred=pred, value=value, mask=ALL, block_rows=br)
+        with pytest.raises(FQError) as e:
+            ops.jit_prepare_typed([dt], value=chain_columns([dt, dt], [load(1), ("+", k)])[0], mask=ALL)
+        assert e.value.status == abi.FQ_E_INVALID and "column index" in str(e.value)
+
+
 # ---------------------------------------------------------------------------
 # validation
 # ---------------------------------------------------------------------------

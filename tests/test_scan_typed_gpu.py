@@ -598,6 +598,27 @@ def test_all_64_bit_columns_return_the_bytes_of_aggregate_columns():
     assert bytes(ops.aggregate_typed(one, 10000, None, v1, ALL)) == bytes(ops.aggregate_columns(one, 10000, None, v1, ALL))
 
 
+def test_one_64_bit_column_with_a_load_of_its_one_column():
+    """load(0) over one 64-bit column is the program without it (tests/test_fuzz_typed_gpu.py agg seed 17: the
+    single-column entry point such a call becomes refused FQ_OP_LOAD as "fq_step: bad op")"""
+    n = 30017
+    a = np.random.default_rng(18).integers(-(1 << 40), 1 << 40, n).astype(np.int64)
+    steps = [("%", (3, "Int64")), ("/", (2147483647, "Int32"))]
+    value, vdt = chain_columns([I64], [load(0)] + steps)
+    plain, _ = chain_columns([I64], steps)
+    assert vdt == I64
+    pred = predicate_columns([I64], [load(0)], ">=", (-5, "Int64"))
+    where = R.Compare(">=", fld("a"), const(-5, "Int64"))
+    arg = R.Arith("/", R.Arith("%", fld("a"), const(3, "Int64")), const(2147483647, "Int32"))
+    for br, off in ((0, 0), (0, 1), (10000, 0)):
+        cols = [numpy_dev(a, I64, off)]
+        st = ops.aggregate_typed(cols, br, pred, value, ALL)
+        check(st, ref_scan(["a"], [I64], [a], where, arg, br), ALL, "load(0) br=%d" % br)
+        assert bytes(st) == bytes(ops.aggregate_typed(cols, br, predicate_columns([I64], [], ">=", (-5, "Int64")), plain, ALL))
+        lone = ops.aggregate_typed(cols, br, None, chain_columns([I64], [load(0)])[0], ALL)
+        assert bytes(lone) == bytes(ops.aggregate_typed(cols, br, None, None, ALL))
+
+
 def test_arguments_are_checked():
     from fq_amd._lib import FQError
     a = numpy_dev(np.arange(100, dtype=np.int32), I32, 0)

@@ -208,6 +208,41 @@ void append_block(fq_result *r, fq::DataBlock b0, fq::ExecCtx &ctx) {
     r->rows += n;
 }
 
+// The 32-bit delta copy of a resident UInt64 column (fq_for32_encode), or null
+// -- never an error -- when the device has less than twice its bytes free, the
+// allocation fails, or a frame of the column spans more than 32 bits.  One
+// allocation: deltas, bases, then the encoder's flag word.
+std::shared_ptr<const fq::For32Sidecar> try_for32(const fq::Column &c, fq::ExecCtx &ctx) {
+    const size_t db = fq_for32_delta_bytes(c.len), bb = fq_for32_base_bytes(c.len);
+    const size_t bytes = db + bb + 256;
+    size_t free_b = 0, total = 0;
+    if (hipMemGetInfo(&free_b, &total) != hipSuccess || free_b < 2 * bytes) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    auto mem = std::make_shared<fq::DeviceBuffer>();
+    mem->async = false;
+    if (hipMalloc(&mem->ptr, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        mem->ptr = nullptr;
+        return nullptr;
+    }
+    mem->bytes = bytes;
+    auto side = std::make_shared<fq::For32Sidecar>();
+    side->mem = mem;
+    side->len = c.len;
+    side->frames = fq_for32_frames(c.len);
+    uint32_t *d_flag = (uint32_t *)((char *)mem->ptr + db + bb);
+    const fq_col col = c.abi();
+    fq::check_fq(fq_for32_encode(&col, (uint64_t *)side->base(), (uint32_t *)side->delta(), d_flag, ctx.stream()));
+    uint32_t flag = 0;
+    fq::check_hip(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx.stream()),
+                  "hipMemcpyAsync(for32 flag)");
+    ctx.sync();
+    if (flag) return nullptr;  // not encodable: the buffers go with `mem`
+    return side;
+}
+
 const fq::PlanNode *aggregate_node(const fq::QueryPlan &p) {
     for (const auto &n : p.nodes)
         if (n.kind == fq::PlanNode::kAggregate) return &n;
@@ -273,6 +308,11 @@ fq_status fq_engine_set_option(fq_engine *e, int32_t option, int64_t value) {
                 if (value < 0) throw fq::FQException(FQ_E_INVALID, "FQ_OPT_FAULT_PIPE is 0 or a pipe number");
                 e->rt->fault_pipe.store(value);
                 break;
+            case FQ_OPT_RESIDENT_FOR32:
+                if (value != 0 && value != 1)
+                    throw fq::FQException(FQ_E_INVALID, "FQ_OPT_RESIDENT_FOR32 is 0 or 1");
+                e->rt->resident_for32.store((int)value);
+                break;
             default: throw fq::FQException(FQ_E_INVALID, "fq_engine_set_option: unknown option");
         }
     });
@@ -300,6 +340,17 @@ fq_status fq_engine_materialize_numbers(fq_engine *e, uint64_t total, int32_t ra
             fq::check_fq(fq_fill_numbers_u64((uint64_t *)c.dptr(), b, rows, ctx.stream()));
             c.iota = true;
             ctx.sync();
+            e->ds->numbers()->pin(parts[i].name, c);
+        }
+        // Every plain partition is resident: now each one's 32-bit delta copy,
+        // where it fits and encodes (a partition without one is scanned plain)
+        if (!e->rt->resident_for32.load()) return;
+        for (size_t i = lo; i < hi; ++i) {
+            fq::Column c;
+            if (!e->ds->numbers()->pinned(parts[i].name, c) || c.len == 0) continue;
+            auto side = try_for32(c, ctx);
+            if (!side) continue;
+            c.for32 = side;
             e->ds->numbers()->pin(parts[i].name, c);
         }
     });

@@ -926,6 +926,7 @@ Column Column::slice(int64_t start, int64_t n) const {
     if (start > len) start = len;
     if (n > len - start) n = len - start;
     c.len = n;
+    if (start != 0 || n != len) c.for32.reset();  // the delta copy stands for the whole column only
     if (host) {
         c.host = std::make_shared<std::vector<DataValue>>(host->begin() + start, host->begin() + start + n);
     } else if (flat) {

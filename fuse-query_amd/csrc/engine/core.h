@@ -237,6 +237,9 @@ class Runtime {
     std::atomic<int64_t> group_chunk_rows{500000000};
     // FQ_OPT_FAULT_PIPE (testing): merged pipe k (1-based) fails its context setup
     std::atomic<int64_t> fault_pipe{0};
+    // FQ_OPT_RESIDENT_FOR32: build and scan the resident partitions' 32-bit delta copies (a host opts in:
+    // the copies cost 4 B per row of HBM beside the plain 8, and the scans' statistics change with them)
+    std::atomic<int> resident_for32{0};
     ThreadPool pool;
 
    private:
@@ -334,6 +337,15 @@ class ExecCtx {
 // ---------------------------------------------------------------------------
 // columns and blocks
 // ---------------------------------------------------------------------------
+// A resident UInt64 column's frame-of-reference copy (fq_for32_encode): one
+// allocation, the deltas (fq_for32_delta_bytes) then the frame bases.
+struct For32Sidecar {
+    std::shared_ptr<DeviceBuffer> mem;
+    int64_t len = 0, frames = 0;
+    const uint32_t *delta() const { return (const uint32_t *)mem->ptr; }
+    const uint64_t *base() const { return (const uint64_t *)((const char *)mem->ptr + fq_for32_delta_bytes(len)); }
+};
+
 struct Column {
     DataType dtype = FQ_DT_NULL;
     int64_t len = 0;
@@ -346,6 +358,9 @@ struct Column {
     std::shared_ptr<std::vector<uint64_t>> flat;
     // consecutive integers v[0], v[0] + 1, ... (a numbers_mt block; slices keep it)
     bool iota = false;
+    // the whole column once more as 32-bit deltas (a resident partition);
+    // slice() keeps it only for the whole column
+    std::shared_ptr<const For32Sidecar> for32;
 
     bool on_device() const { return (bool)dev; }
     void *dptr() const { return dev ? (char *)dev->ptr + offset : nullptr; }

@@ -1417,6 +1417,9 @@ void AggFusion::add(AggregatorFunction *agg, const DataBlock &b) {
         g->typed = typed;
         if (cols.names.size() > 1 || typed)
             for (const std::string &name : cols.names) g->cols.push_back(b.column_by_name(name));
+        else if (!b.filter && fc.expr.n_steps == 0 && g->col.dtype == FQ_DT_UINT64 && g->col.for32 &&
+                 g->col.for32->len == g->col.len && ctx_.rt->resident_for32.load())
+            g->for32 = g->col.for32;
         g->value = fc;
         g->value_expr = value_expr;
         g->has_pred = (bool)b.filter;
@@ -1490,6 +1493,9 @@ void AggFusion::end_block() {
                 check_fq((g.typed ? fq_aggregate_typed : fq_aggregate_columns)(
                     cs, n_cols, g.block_rows, pred, g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask,
                     (fq_agg_state *)dst, res_->ws, res_->ws_bytes, stream_));
+            else if (g.for32)
+                check_fq(fq_aggregate_for32(g.for32->delta(), g.for32->base(), g.for32->len, g.mask,
+                                            (fq_agg_state *)dst, res_->ws, res_->ws_bytes, stream_));
             else
                 check_fq(fq_aggregate(&c, g.block_rows, pred, val, g.mask, (fq_agg_state *)dst, res_->ws,
                                       res_->ws_bytes, stream_));
@@ -1504,7 +1510,9 @@ void AggFusion::end_block() {
         // every column of the scan is read once: the sum of the widths x rows
         uint64_t row_bytes = n_cols ? 0 : (uint64_t)dtype_size(g.col.dtype);
         for (const Column &gc : g.cols) row_bytes += (uint64_t)dtype_size(gc.dtype);
-        ctx_.rt->stats.scan_bytes += (uint64_t)g.col.len * row_bytes;
+        // (a delta copy: 4 bytes per row and a base per frame)
+        if (g.for32) ctx_.rt->stats.scan_bytes += (uint64_t)g.col.len * 4u + (uint64_t)g.for32->frames * 8u;
+        else ctx_.rt->stats.scan_bytes += (uint64_t)g.col.len * row_bytes;
         for (const uint64_t *v : g.validity)  // and a bit per row of every bitmap
             if (v) ctx_.rt->stats.scan_bytes += ((uint64_t)g.col.len + 7) / 8;
         // a stream-ordered column (hipFreeAsync on the queue the scan was just

@@ -292,6 +292,132 @@ __global__ void __launch_bounds__(kThreads)
     reduce_and_store<V>(acc, parts + blockIdx.x, vdtype);
 }
 
+// ---------------------------------------------------------------------------
+// Frame-of-reference storage of a resident UInt64 column (fq_for32_encode /
+// fq_aggregate_for32): frame f = rows [f F, (f + 1) F), F = FQ_FOR32_FRAME_ROWS,
+// is base[f] = its minimum and delta[i] = value[i] - base[i / F] in 32 bits.
+// The scan reads 4 bytes per row instead of 8; sum (wrapping), max, min and
+// count over base + delta are the plain column's, bit for bit.
+// ---------------------------------------------------------------------------
+constexpr int64_t kFrame = FQ_FOR32_FRAME_ROWS;
+constexpr int64_t kFor32Tile = 4 * kThreads * 4;  // rows of a tile: 4 vectors x 256 lanes x 4 u32 (16 KB)
+static_assert(kFrame % kFor32Tile == 0, "a tile never straddles a frame");
+
+// One workgroup per frame (a grid stride over frames): the frame's minimum and
+// maximum from the data, then its deltas (the second read of the 512 KB frame
+// comes from L2).  *flag = 1 when a frame spans more than 32 bits.
+__global__ void __launch_bounds__(kThreads)
+    for32_encode_kernel(const uint64_t *__restrict__ col, int64_t n, uint64_t *__restrict__ base,
+                        uint32_t *__restrict__ delta, uint32_t *flag) {
+    __shared__ uint64_t s_mn[kThreads / kWave], s_mx[kThreads / kWave];
+    const int64_t frames = (n + kFrame - 1) / kFrame;
+    for (int64_t f = blockIdx.x; f < frames; f += gridDim.x) {
+        const int64_t s = f * kFrame;
+        const int64_t e = s + kFrame < n ? s + kFrame : n;
+        uint64_t mn = ~0ull, mx = 0;
+        for (int64_t i = s + threadIdx.x; i < e; i += kThreads) {
+            const uint64_t v = col[i];
+            mn = v < mn ? v : mn;
+            mx = v > mx ? v : mx;
+        }
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+            mn = vmin(mn, shfl_xor64(mn, off));
+            mx = vmax(mx, shfl_xor64(mx, off));
+        }
+        __syncthreads();  // the previous frame's s_mn / s_mx have been read
+        if ((threadIdx.x & (kWave - 1)) == 0) {
+            s_mn[threadIdx.x / kWave] = mn;
+            s_mx[threadIdx.x / kWave] = mx;
+        }
+        __syncthreads();
+        mn = s_mn[0];
+        mx = s_mx[0];
+#pragma unroll
+        for (int w = 1; w < kThreads / kWave; ++w) {
+            mn = vmin(mn, s_mn[w]);
+            mx = vmax(mx, s_mx[w]);
+        }
+        if (threadIdx.x == 0) {
+            base[f] = mn;
+            if (mx - mn > 0xFFFFFFFFull) *flag = 1u;
+        }
+        for (int64_t i = s + threadIdx.x; i < e; i += kThreads) delta[i] = (uint32_t)(col[i] - mn);
+    }
+}
+
+// agg_flat_kernel's streaming loop over the 32-bit deltas: a workgroup reads
+// one contiguous 16 KB tile (4 non-temporal 16-byte loads per lane) per
+// iteration and strides over tiles by the grid.  Per row the work is 32-bit; a
+// lane folds its 16 deltas of a tile into its 64-bit accumulators once, with
+// the tile's frame base (workgroup-uniform).  Vectors past the last whole tile
+// and the up to 3 rows after them look their base up from the row index.
+__global__ void __launch_bounds__(kThreads)
+    agg_flat_kernel_for32(const uint32_t *__restrict__ delta, const uint64_t *__restrict__ base, int64_t n,
+                          uint32_t mask, Partial *parts) {
+    constexpr int U = 4, VE = 4, E = U * VE;
+    constexpr int64_t TV = (int64_t)U * kThreads;   // vectors per tile
+    constexpr int64_t kTilesPerFrame = kFrame / kFor32Tile;
+    Acc<uint64_t> acc;
+    acc.init();
+    const int64_t T = (int64_t)gridDim.x * kThreads;
+    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int64_t nvec = n / VE;
+    const int64_t ntiles = nvec / TV;
+    const u32x4 *__restrict__ vp = reinterpret_cast<const u32x4 *>(delta);
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int64_t v0 = t * TV + threadIdx.x;
+        u32x4 raw[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) raw[k] = __builtin_nontemporal_load(vp + v0 + (int64_t)k * kThreads);
+        const uint64_t b = base[t / kTilesPerFrame];
+        uint32_t x[E];
+#pragma unroll
+        for (int k = 0; k < U; ++k) __builtin_memcpy(&x[k * VE], &raw[k], 16);
+        if (mask & FQ_AGG_SUM) {
+            uint64_t dsum = 0;
+#pragma unroll
+            for (int j = 0; j < E; ++j) dsum += x[j];
+            acc.sum += dsum + (uint64_t)E * b;
+        }
+        if (mask & FQ_AGG_MAX) {
+            uint32_t dmax = 0;
+#pragma unroll
+            for (int j = 0; j < E; ++j) dmax = x[j] > dmax ? x[j] : dmax;
+            acc.mx = vmax(acc.mx, b + dmax);
+        }
+        if (mask & FQ_AGG_MIN) {
+            uint32_t dmin = 0xFFFFFFFFu;
+#pragma unroll
+            for (int j = 0; j < E; ++j) dmin = x[j] < dmin ? x[j] : dmin;
+            acc.mn = vmin(acc.mn, b + dmin);
+        }
+        acc.cnt += E;
+    }
+    for (int64_t v = ntiles * TV + g; v < nvec; v += T) {
+        const u32x4 raw = __builtin_nontemporal_load(vp + v);
+        const uint64_t b = base[(v * VE) / kFrame];  // a 4-row vector never straddles a frame
+        uint32_t x[VE];
+        __builtin_memcpy(&x[0], &raw, 16);
+#pragma unroll
+        for (int j = 0; j < VE; ++j) {
+            const uint64_t val = b + x[j];
+            if (mask & FQ_AGG_SUM) acc.sum += val;
+            if (mask & FQ_AGG_MAX) acc.mx = vmax(acc.mx, val);
+            if (mask & FQ_AGG_MIN) acc.mn = vmin(acc.mn, val);
+        }
+        acc.cnt += VE;
+    }
+    for (int64_t i = nvec * VE + g; i < n; i += T) {
+        const uint64_t val = base[i / kFrame] + delta[i];
+        if (mask & FQ_AGG_SUM) acc.sum += val;
+        if (mask & FQ_AGG_MAX) acc.mx = vmax(acc.mx, val);
+        if (mask & FQ_AGG_MIN) acc.mn = vmin(acc.mn, val);
+        acc.cnt += 1;
+    }
+    reduce_and_store<uint64_t>(acc, parts + blockIdx.x, FQ_DT_UINT64);
+}
+
 // Block mode: one wave owns whole reference blocks of R rows; one ballot per
 // block tells whether any of its rows survived the predicate.
 template <typename TIn, typename V, int PRED, bool CHAIN, int U>
@@ -1440,6 +1566,67 @@ fq_status fq_jit_prepare_columns(const fq_col *cols, int32_t n_cols, int64_t blo
 fq_status fq_aggregate(const fq_col *col, int64_t block_rows, const fq_pred *pred, const fq_expr *value,
                        uint32_t agg_mask, fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream) {
     return fqk::aggregate(col, block_rows, pred, value, agg_mask, d_out, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+int64_t fq_for32_frames(int64_t len) { return len <= 0 ? 0 : (len + fqk::kFrame - 1) / fqk::kFrame; }
+
+size_t fq_for32_delta_bytes(int64_t len) { return len <= 0 ? 0 : (((size_t)len * 4 + 255) / 256) * 256; }
+
+size_t fq_for32_base_bytes(int64_t len) { return (size_t)fq_for32_frames(len) * 8; }
+
+fq_status fq_for32_encode(const fq_col *col, uint64_t *d_base, uint32_t *d_delta, uint32_t *d_flag, void *stream) {
+    using namespace fqk;
+    if (!col || !d_flag) return fqc::fail(FQ_E_INVALID, "fq_for32_encode: NULL argument");
+    if (col->len < 0) return fqc::fail(FQ_E_INVALID, "fq_for32_encode: negative length");
+    if (col->dtype != FQ_DT_UINT64)
+        return fqc::fail(FQ_E_UNSUPPORTED, std::string("fq_for32_encode: ") + fqc::dtype_name(col->dtype) +
+                                               " column (the encoding is defined for UInt64)");
+    if (col->len > 0 && (!col->data || !d_base || !d_delta))
+        return fqc::fail(FQ_E_INVALID, "fq_for32_encode: NULL argument");
+    if (((uintptr_t)col->data) % 8 || ((uintptr_t)d_base) % 8)
+        return fqc::fail(FQ_E_INVALID, "fq_for32_encode: column / base not aligned to 8 bytes");
+    if (((uintptr_t)d_delta) % 16) return fqc::fail(FQ_E_INVALID, "fq_for32_encode: delta not aligned to 16 bytes");
+    FQ_HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), (hipStream_t)stream));
+    if (col->len == 0) return FQ_OK;
+    const int64_t frames = fq_for32_frames(col->len);
+    const int64_t max_grid = (int64_t)fqc::device_cu_count() * 8;
+    const int grid = (int)(frames < max_grid ? frames : max_grid);
+    hipLaunchKernelGGL(for32_encode_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
+                       (const uint64_t *)col->data, col->len, d_base, d_delta, d_flag);
+    FQ_HIP_TRY(hipGetLastError());
+    return FQ_OK;
+}
+
+fq_status fq_aggregate_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t len, uint32_t agg_mask,
+                             fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream) {
+    using namespace fqk;
+    if (!d_out || !d_ws) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: NULL argument");
+    if (len < 0) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: negative length");
+    if (ws_bytes < kPartialsBytes) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: workspace too small");
+    if (agg_mask & ~(uint32_t)(FQ_AGG_MIN | FQ_AGG_MAX | FQ_AGG_SUM | FQ_AGG_COUNT))
+        return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: unknown bits in agg_mask");
+    if (((uintptr_t)d_delta) % 16) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: delta not aligned to 16 bytes");
+    if (((uintptr_t)d_base) % 8) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: base not aligned to 8 bytes");
+    Launch L{};
+    L.n = len;
+    L.mask = agg_mask;
+    L.vdtype = FQ_DT_UINT64;
+    L.parts = (Partial *)d_ws;
+    L.stream = (hipStream_t)stream;
+    const uint64_t blocks = len > 0 ? 1 : 0;  // one block, as fq_aggregate with block_rows = 0
+    if (agg_mask == FQ_AGG_COUNT) {
+        L.grid = 0;  // count(column): rows, not values (see launch_finalize)
+        return dispatch_finalize(L, blocks, 0, d_out);
+    }
+    if (len > 0 && (!d_delta || !d_base)) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: NULL argument");
+    int64_t grid = (len / 4 + kFor32Tile / 4 - 1) / (kFor32Tile / 4);
+    if (grid < 1) grid = 1;
+    const int64_t flat_max = (int64_t)fqc::device_cu_count() * scan_wg_per_cu();
+    L.grid = (int)(grid < flat_max ? grid : flat_max);
+    hipLaunchKernelGGL(agg_flat_kernel_for32, dim3(L.grid), dim3(kThreads), 0, L.stream, d_delta, d_base, len,
+                       agg_mask, L.parts);
+    FQ_HIP_TRY(hipGetLastError());
+    return dispatch_finalize(L, blocks, 0, d_out);
 }
 
 fq_status fq_jit_prepare(const fq_col *col, int64_t block_rows, const fq_pred *pred, const fq_expr *value,

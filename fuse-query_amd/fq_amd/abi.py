@@ -50,6 +50,8 @@ MAX_STACK = 2
 PRED_NONE, PRED_EXPR, PRED_BITMAP = 0, 1, 2
 MAX_STEPS = 8
 
+FOR32_FRAME_ROWS = 65536  # rows per frame of fq_for32_encode / fq_aggregate_for32
+
 STATE_ANY_EMPTY = 1
 STATE_DIV_ZERO = 2
 STATE_CAST_NULL = 4

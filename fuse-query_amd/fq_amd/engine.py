@@ -21,6 +21,7 @@ P = C.POINTER
 
 OPT_WORKER_THREADS, OPT_MODULO, OPT_PROFILE, OPT_STREAMS, OPT_CHUNK_ROWS, OPT_GROUP_CHUNK_ROWS = 1, 2, 3, 4, 5, 6
 OPT_FAULT_PIPE = 7  # testing: merged pipe k (1-based) fails its device-context setup
+OPT_RESIDENT_FOR32 = 8  # 1: resident partitions also kept, and scanned, as per-frame 32-bit deltas (Engine's default)
 PROFILE_PAIRS, PROFILE_SPAN = 1, 2  # FQ_OPT_PROFILE values
 
 ENGINE_SYMBOLS = [
@@ -250,7 +251,7 @@ class BlockStream:
 
 
 class Engine:
-    def __init__(self, device=0, worker_threads=8, modulo=True, profile=False, streams=1):
+    def __init__(self, device=0, worker_threads=8, modulo=True, profile=False, streams=1, resident_for32=True):
         import weakref
         self._streams = weakref.WeakSet()  # open BlockStreams
         h = C.c_void_p()
@@ -262,6 +263,9 @@ class Engine:
         # (= 2, one span from a query's first scan to its last, fq_engine.h)
         self.set_option(OPT_PROFILE, int(profile))
         self.set_option(OPT_STREAMS, streams)
+        # resident partitions also kept, and scanned, as 32-bit deltas (fq_engine.h); None: the library's default (off)
+        if resident_for32 is not None:
+            self.set_option(OPT_RESIDENT_FOR32, 1 if resident_for32 else 0)
 
     def set_option(self, opt, value):
         check(lib.fq_engine_set_option(self.h, opt, int(value)))

@@ -258,6 +258,47 @@ def aggregate_nullable(cols, validity, block_rows=0, pred=None, value=None, mask
     return abi.fq_agg_state_n.from_buffer_copy(t.cpu().numpy().tobytes())
 
 
+class For32Column:
+    """A UInt64 column as fq_for32_encode stores it: `delta` (UInt32, one per
+    row) and `base` (UInt64, one per frame of abi.FOR32_FRAME_ROWS rows)."""
+
+    def __init__(self, delta, base, length):
+        self.delta = delta
+        self.base = base
+        self.len = int(length)
+
+    def decode(self):
+        """base[i / F] + delta[i] on the host (numpy uint64, wrapping)."""
+        d = self.delta.to_numpy().astype(np.uint64)
+        b = self.base.to_numpy()
+        return d + np.repeat(b, abi.FOR32_FRAME_ROWS)[: self.len]
+
+
+def for32_encode(col, stream=None):
+    """fq_for32_encode of a UInt64 DeviceColumn -> (For32Column, encodable)."""
+    require_gpu()
+    n = col.len
+    delta = DeviceColumn(torch.empty(max(lib.fq_for32_delta_bytes(n), 256), dtype=torch.uint8, device="cuda"), n,
+                         abi.DT_UINT32)
+    base = DeviceColumn(torch.empty(max(lib.fq_for32_base_bytes(n), 256), dtype=torch.uint8, device="cuda"),
+                        lib.fq_for32_frames(n), abi.DT_UINT64)
+    flag = torch.empty(1, dtype=torch.int32, device="cuda")
+    c = col.col()
+    check(lib.fq_for32_encode(C.byref(c), C.c_void_p(base.ptr), C.c_void_p(delta.ptr), C.c_void_p(flag.data_ptr()),
+                              _stream(stream)))
+    return For32Column(delta, base, n), int(flag.cpu().item()) == 0
+
+
+def aggregate_for32(enc, mask=0xF, ws=None, stream=None):
+    """fq_aggregate_for32 over a For32Column -> host fq_agg_state."""
+    require_gpu()
+    ws = ws or Workspace(lib.fq_aggregate_workspace_bytes(enc.len))
+    out = torch.empty(48, dtype=torch.uint8, device="cuda")
+    check(lib.fq_aggregate_for32(C.c_void_p(enc.delta.ptr), C.c_void_p(enc.base.ptr), enc.len, mask,
+                                 C.c_void_p(out.data_ptr()), ws.ptr, ws.nbytes, _stream(stream)))
+    return state_from_device(out)
+
+
 def state_values(st):
     """fq_agg_state -> dict(sum, max, min, count, blocks, flags) of Python values;
     fq_agg_state_n: also `valid`, and sum / max / min are None when valid == 0."""

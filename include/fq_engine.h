@@ -63,6 +63,17 @@ typedef struct fq_result fq_result;
                                    merged queries fails while it sets up its device context, as a
                                    failed workspace allocation would -- the query must return
                                    that error, never wait for the pipe (processor_merge.rs:50-54) */
+#define FQ_OPT_RESIDENT_FOR32 8 /* 1: fq_engine_materialize_numbers also stores each resident
+                                   partition as per-frame 32-bit deltas (fq_for32_encode, 4 B per row
+                                   beside the plain 8), and an unfiltered sum/max/min/count scan of the
+                                   plain column reads those (fq_aggregate_for32; scan_bytes then counts
+                                   4 B per row and 8 B per frame).  0: no such copy is built AND scans
+                                   ignore an existing one -- read at both points, so one process can run
+                                   both paths over the same resident data.  A partition whose copy does
+                                   not fit, or does not encode, is scanned plain.  The library's default
+                                   is 0: a host that sized its HBM for 8 B per resident row, or reads
+                                   scan_bytes as 8 B per row, sees no change until it opts in.  The
+                                   Python binding (fq_amd.engine.Engine) opts in by default */
 
 typedef struct fq_engine_stats {
     uint64_t scan_launches; /* fused aggregate scans launched                    */

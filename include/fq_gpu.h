@@ -350,6 +350,36 @@ fq_status fq_jit_prepare_nullable(const fq_col *cols, const uint8_t *has_validit
                                   int64_t block_rows, const fq_pred *pred, const fq_expr *value,
                                   uint32_t agg_mask, int32_t *specialised);
 
+/* ---- Frame-of-reference storage of a resident UInt64 column (no reference
+ * counterpart: the reference regenerates numbers_mt for every query) ----
+ * A frame is FQ_FOR32_FRAME_ROWS consecutive rows.  An encoded column is
+ *   base[fq_for32_frames(len)]  each frame's minimum, and
+ *   delta[len]                  delta[i] = value[i] - base[i / FQ_FOR32_FRAME_ROWS]
+ * in 32 bits: half the bytes of the plain column wherever the values of a
+ * frame span less than 2^32.  Lossless: base[i / F] + delta[i] is value[i].
+ * fq_for32_delta_bytes / fq_for32_base_bytes size the two buffers (delta
+ * rounded up to 256 bytes); delta must be 16-byte aligned.
+ *
+ * fq_for32_encode computes every frame's minimum and maximum from the data,
+ * writes bases and deltas, and leaves *d_flag (4 bytes of device memory, zeroed
+ * by the call) 0, or 1 when some frame has max - min > 0xFFFFFFFF: the column
+ * is then not encodable and the buffers' contents are to be discarded.
+ * Asynchronous on `stream`; the caller reads the flag after waiting for it.
+ *
+ * fq_aggregate_for32 is fq_aggregate over the encoded column with block_rows
+ * = 0, no predicate and no expression: the same fq_agg_state, bit for bit
+ * (wrapping sum, max, min, count, flags 0, dtype UInt64), from 4 bytes per row
+ * read.  Workspace and the fixed-order fold are fq_aggregate's; a request for
+ * count alone reads nothing.  FQ_E_INVALID for a delta pointer that is not
+ * 16-byte aligned or unknown bits in agg_mask.                              */
+#define FQ_FOR32_FRAME_ROWS 65536
+int64_t fq_for32_frames(int64_t len);
+size_t fq_for32_delta_bytes(int64_t len);
+size_t fq_for32_base_bytes(int64_t len);
+fq_status fq_for32_encode(const fq_col *col, uint64_t *d_base, uint32_t *d_delta, uint32_t *d_flag, void *stream);
+fq_status fq_aggregate_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t len, uint32_t agg_mask,
+                             fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream);
+
 /* ---- ArithmeticFunction::eval (data_array_arithmetic.rs:14-55) ----
  * Exactly one of {lhs, lhs_scalar} and one of {rhs, rhs_scalar} is non-NULL.
  * out->data must hold out->len elements of the coercion type returned by

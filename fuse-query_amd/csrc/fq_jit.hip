@@ -1914,25 +1914,31 @@ __device__ __forceinline__ u32 gp_rank(u32 *cnt, u32 b, bool p) {
 }
 
 #if GP_MOD32
-// key = x % d for a 4-byte row: x = mbase + a with a < 2^32 (mbase = the
-// narrow rows' base, or 0 when that base would wrap: the values then lie
-// below 2^32), so x % d = (mbase % d + a % d) mod d, a % d by Lemire's direct
-// remainder (M = floor((2^64 - 1) / d) + 1, exact for 32-bit a and d)
+// key = x % d for a 4-byte row: x = mbase + a modulo 2^64 with a < 2^32 and
+// mbase = the narrow rows' base col[0] - 2^31 (modulo 2^64).  Where mbase + a
+// stays below 2^64, x % d = (mbase % d + a % d) mod d; where it passes 2^64
+// (col[0] < 2^31 and x at or above it, or col[0] near 2^64 and x past zero)
+// x itself is below 2^32 and x % d is taken directly.  Either remainder by
+// Lemire's direct remainder (M = floor((2^64 - 1) / d) + 1, exact for 32-bit
+// arguments and d)
 struct GMod { u64 mbase, M; u32 d, cb; };
 __device__ __forceinline__ GMod gp_mod_init(u64 c0, const Consts &c) {
     GMod m;
-    m.mbase = c0 >= 0x80000000ull ? c0 - 0x80000000ull : 0ull;
+    m.mbase = c0 - 0x80000000ull;
     m.d = (u32)c.k[0].c;
     m.M = 0xffffffffffffffffull / (u64)m.d + 1ull;
     m.cb = (u32)(m.mbase % (u64)m.d);
     return m;
 }
 __device__ __forceinline__ u32 gp_key32(TIn x, const GMod &m) {
-    const u64 low = m.M * (u64)(u32)((u64)x - m.mbase);
+    const u32 a = (u32)((u64)x - m.mbase);
+    const bool wrapped = (u64)a > ~m.mbase;  // mbase + a passes 2^64: x = its low 32 bits
+    const u64 low = m.M * (u64)(wrapped ? (u32)(u64)x : a);
     const u64 t = ((u64)(u32)low * m.d) >> 32;
     const u32 r = (u32)(((low >> 32) * m.d + t) >> 32);
-    const u32 k = m.cb + r;  // cb, r < d: a sum >= d, or one that wrapped 32 bits, loses one d
-    return k >= m.d || k < m.cb ? k - m.d : k;
+    const u32 cb = wrapped ? 0u : m.cb;
+    const u32 k = cb + r;  // cb, r < d: a sum >= d, or one that wrapped 32 bits, loses one d
+    return k >= m.d || k < cb ? k - m.d : k;
 }
 #endif
 __device__ __forceinline__ long long gp_row(long long tt, int k) {

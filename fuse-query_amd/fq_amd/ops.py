@@ -735,7 +735,7 @@ class GroupTable:
     def aggregate(self, col, pred=None, key=None, values=None, stream=None, log2_parts=0, narrow=False):
         """fq_group_aggregate, or with log2_parts > 0 the radix-partitioned
         fq_group_aggregate_partitioned (2^log2_parts bins; narrow: the caller
-        vouches every value lies within 2^31 of the first, FQ_GROUP_NARROW_ROWS)."""
+        vouches every value v has col[0] - 2^31 <= v <= col[0] + 2^31 - 1, FQ_GROUP_NARROW_ROWS)."""
         c = col.col()
         vals = (abi.fq_expr * abi.MAX_GROUP_AGGS)()
         for i, v in enumerate(values or []):
@@ -805,6 +805,12 @@ def group_compile_check(col_dtype, aggs, key=None, values=None, pred=None, key_d
         check(lib.fq_group_aggregate_partitioned(C.byref(d), C.byref(c), p, k, vals, log2_parts, None, 0, None))
     else:
         check(lib.fq_group_aggregate(C.byref(d), C.byref(c), p, k, vals, None))
+
+
+def group_dense_keys(col_dtype, key, n_aggs):
+    """fq_group_dense_keys: d when the key over a column of col_dtype ends in `% d` and d fits the GROUP BY
+    kernel's LDS table for n_aggs states (the table is then indexed by the key itself), else 0."""
+    return int(lib.fq_group_dense_keys(col_dtype, C.byref(key) if key is not None else None, n_aggs))
 
 
 def tune_set(name, value):

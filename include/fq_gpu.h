@@ -683,8 +683,9 @@ fq_status fq_group_aggregate(const fq_group_table *t, const fq_col *col, const f
  * fq_group_partition_workspace_bytes(col->len, log2_parts) bytes (about 8 B
  * per row plus ~2 KB per (workgroup, bin) chain).  Asynchronous. */
 /* FQ_GROUP_NARROW_ROWS or-ed into log2_parts: the caller guarantees that every
- * value v of the (8-byte integer) column lies within 2^31 of col[0] (e.g. a
- * numbers_mt block: consecutive integers).  The partition pass then writes
+ * value v of the (8-byte integer) column satisfies col[0] - 2^31 <= v <=
+ * col[0] + 2^31 - 1, modulo 2^64 (e.g. a numbers_mt block: consecutive
+ * integers; col[0] + 2^31 itself is outside).  The partition pass then writes
  * each kept row as a 4-byte offset from col[0] - 2^31 instead of the 8-byte
  * value: 16 B of HBM traffic per kept row instead of 24.  A value outside
  * the range is reported at count/extract (FQ_E_INVALID); Float64 columns

@@ -313,6 +313,11 @@ fq_status fq_engine_set_option(fq_engine *e, int32_t option, int64_t value) {
                     throw fq::FQException(FQ_E_INVALID, "FQ_OPT_RESIDENT_FOR32 is 0 or 1");
                 e->rt->resident_for32.store((int)value);
                 break;
+            case FQ_OPT_RESIDENT_FOR32_FUSED:
+                if (value != 0 && value != 1)
+                    throw fq::FQException(FQ_E_INVALID, "FQ_OPT_RESIDENT_FOR32_FUSED is 0 or 1");
+                e->rt->resident_for32_fused.store((int)value);
+                break;
             default: throw fq::FQException(FQ_E_INVALID, "fq_engine_set_option: unknown option");
         }
     });

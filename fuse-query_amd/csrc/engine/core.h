@@ -240,6 +240,9 @@ class Runtime {
     // FQ_OPT_RESIDENT_FOR32: build and scan the resident partitions' 32-bit delta copies (a host opts in:
     // the copies cost 4 B per row of HBM beside the plain 8, and the scans' statistics change with them)
     std::atomic<int> resident_for32{0};
+    // FQ_OPT_RESIDENT_FOR32_FUSED: with resident_for32, scans with a fused predicate or argument
+    // expression read the delta copies too (fq_aggregate_for32_expr) where the JIT specialises them
+    std::atomic<int> resident_for32_fused{0};
     ThreadPool pool;
 
    private:

@@ -234,6 +234,14 @@ DataValue ArithmeticFunction::merge_result() const {
     return data_value_arithmetic_op(op_, left_->merge_result(), right_->merge_result());
 }
 
+// A fused one-column scan of `len` rows runs on its hipRTC kernel (not on the
+// interpreting one): what a scan over a delta copy needs (FQ_OPT_RESIDENT_FOR32_FUSED)
+static bool jit_will_specialise(int64_t len) {
+    fq_jit_stats js;
+    if (fq_jit_get_stats(&js) != FQ_OK || js.available == 0) return false;
+    return js.mode == FQ_JIT_ALWAYS || (js.mode == FQ_JIT_AUTO && len >= js.min_rows);
+}
+
 // Expression trees run on the hipRTC kernels only: fuse them while the JIT is
 // on (FQ_JIT / fq_jit_config) and hipRTC has not been found missing.
 static bool tree_fusion_enabled() {
@@ -1417,8 +1425,10 @@ void AggFusion::add(AggregatorFunction *agg, const DataBlock &b) {
         g->typed = typed;
         if (cols.names.size() > 1 || typed)
             for (const std::string &name : cols.names) g->cols.push_back(b.column_by_name(name));
-        else if (!b.filter && fc.expr.n_steps == 0 && g->col.dtype == FQ_DT_UINT64 && g->col.for32 &&
-                 g->col.for32->len == g->col.len && ctx_.rt->resident_for32.load())
+        else if (g->col.dtype == FQ_DT_UINT64 && g->col.for32 && g->col.for32->len == g->col.len &&
+                 ctx_.rt->resident_for32.load() &&
+                 ((!b.filter && fc.expr.n_steps == 0) ||
+                  (ctx_.rt->resident_for32_fused.load() && jit_will_specialise(g->col.len))))
             g->for32 = g->col.for32;
         g->value = fc;
         g->value_expr = value_expr;
@@ -1467,6 +1477,9 @@ void AggFusion::end_block() {
             check_fq((g.typed ? fq_jit_prepare_typed : fq_jit_prepare_columns)(
                 cs, n_cols, g.block_rows, g.has_pred ? g.pred.get() : nullptr,
                 g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask, nullptr));
+        } else if (prof && g.for32 && (g.has_pred || g.value.expr.n_steps)) {
+            check_fq(fq_jit_prepare_for32(g.for32->len, g.block_rows, g.has_pred ? g.pred.get() : nullptr,
+                                          g.value.expr.n_steps ? &g.value.expr : nullptr, g.mask, nullptr));
         } else if (prof && (g.has_pred || g.value.expr.n_steps)) {
             // compile a specialised scan (first use of this expression shape)
             // outside the timed region (identity scans are precompiled)
@@ -1493,6 +1506,9 @@ void AggFusion::end_block() {
                 check_fq((g.typed ? fq_aggregate_typed : fq_aggregate_columns)(
                     cs, n_cols, g.block_rows, pred, g.value_expr.n_steps ? &g.value_expr : nullptr, g.mask,
                     (fq_agg_state *)dst, res_->ws, res_->ws_bytes, stream_));
+            else if (g.for32 && (pred || val))
+                check_fq(fq_aggregate_for32_expr(g.for32->delta(), g.for32->base(), g.for32->len, g.block_rows, pred,
+                                                 val, g.mask, (fq_agg_state *)dst, res_->ws, res_->ws_bytes, stream_));
             else if (g.for32)
                 check_fq(fq_aggregate_for32(g.for32->delta(), g.for32->base(), g.for32->len, g.mask,
                                             (fq_agg_state *)dst, res_->ws, res_->ws_bytes, stream_));

@@ -467,7 +467,8 @@ class AggFusion {
         bool typed = false;        // a narrow column, step or comparison: fq_aggregate_typed over cols (one or more)
         bool nullable = false;     // fq_aggregate_nullable over cols and validity; the slot holds an fq_agg_state_n
         std::vector<const uint64_t *> validity;
-        // the column's 32-bit delta copy: fq_aggregate_for32 (one UInt64 column, no filter, identity argument)
+        // the column's 32-bit delta copy: fq_aggregate_for32 (one UInt64 column, no filter, identity argument),
+        // or fq_aggregate_for32_expr (with either, FQ_OPT_RESIDENT_FOR32_FUSED, where the JIT specialises)
         std::shared_ptr<const For32Sidecar> for32;
         fq_expr value_expr{};      // value.expr, FQ_OP_LOAD in front when it starts from another column than 0
         FusedChain value;

@@ -1597,9 +1597,14 @@ fq_status fq_for32_encode(const fq_col *col, uint64_t *d_base, uint32_t *d_delta
     return FQ_OK;
 }
 
-fq_status fq_aggregate_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t len, uint32_t agg_mask,
-                             fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream) {
-    using namespace fqk;
+}  // extern "C"
+
+namespace fqk {
+
+// fq_aggregate_for32, over `blocks` reference blocks (fq_aggregate_for32_expr
+// without predicate and expression passes its block_rows' count)
+static fq_status aggregate_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t len, uint64_t blocks,
+                                 uint32_t agg_mask, fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream) {
     if (!d_out || !d_ws) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: NULL argument");
     if (len < 0) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: negative length");
     if (ws_bytes < kPartialsBytes) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32: workspace too small");
@@ -1613,7 +1618,6 @@ fq_status fq_aggregate_for32(const uint32_t *d_delta, const uint64_t *d_base, in
     L.vdtype = FQ_DT_UINT64;
     L.parts = (Partial *)d_ws;
     L.stream = (hipStream_t)stream;
-    const uint64_t blocks = len > 0 ? 1 : 0;  // one block, as fq_aggregate with block_rows = 0
     if (agg_mask == FQ_AGG_COUNT) {
         L.grid = 0;  // count(column): rows, not values (see launch_finalize)
         return dispatch_finalize(L, blocks, 0, d_out);
@@ -1627,6 +1631,100 @@ fq_status fq_aggregate_for32(const uint32_t *d_delta, const uint64_t *d_base, in
                        agg_mask, L.parts);
     FQ_HIP_TRY(hipGetLastError());
     return dispatch_finalize(L, blocks, 0, d_out);
+}
+
+static bool for32_identity(const fq_pred *pred, const fq_expr *value) {
+    return (!pred || pred->kind == FQ_PRED_NONE) && (!value || value->n_steps <= 0);
+}
+
+static const char *kFor32NeedsJit =
+    "fused scans over 32-bit deltas run on the hipRTC kernel only (FQ_JIT is off or hipRTC is unavailable)";
+
+// The plan of fq_aggregate_for32_expr / fq_jit_prepare_for32 for a call with a
+// predicate or an expression: fq_aggregate's over the UInt64 column the deltas
+// stand for (lowered programs, flat / block mode, blocks), with the flat grid
+// of fq_aggregate_for32.
+static fq_status plan_scan_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t len, int64_t block_rows,
+                                 const fq_pred *pred, const fq_expr *value, uint32_t agg_mask, bool need_data,
+                                 Launch &L, bool &chain, uint64_t &blocks, int &empty_if_zero) {
+    fq_col col{};
+    col.data = (void *)d_delta;
+    col.dtype = FQ_DT_UINT64;
+    col.len = len;
+    fq_status s = plan_scan(&col, block_rows, pred, value, agg_mask, need_data, L, chain, blocks, empty_if_zero);
+    if (s != FQ_OK) return s;
+    L.for32 = true;
+    L.for32_base = d_base;
+    L.head = 0;
+    if (!L.block_mode) L.grid = for32_flat_grid(len, (int64_t)fqc::device_cu_count() * scan_wg_per_cu());
+    return FQ_OK;
+}
+
+}  // namespace fqk
+
+extern "C" {
+
+fq_status fq_aggregate_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t len, uint32_t agg_mask,
+                             fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream) {
+    // one block, as fq_aggregate with block_rows = 0
+    return fqk::aggregate_for32(d_delta, d_base, len, len > 0 ? 1 : 0, agg_mask, d_out, d_ws, ws_bytes, stream);
+}
+
+fq_status fq_aggregate_for32_expr(const uint32_t *d_delta, const uint64_t *d_base, int64_t len, int64_t block_rows,
+                                  const fq_pred *pred, const fq_expr *value, uint32_t agg_mask, fq_agg_state *d_out,
+                                  void *d_ws, size_t ws_bytes, void *stream) {
+    using namespace fqk;
+    if (for32_identity(pred, value)) {
+        if (block_rows <= 0) block_rows = len > 0 ? len : 1;
+        const uint64_t blocks = len <= 0 ? 0 : (uint64_t)((len + block_rows - 1) / block_rows);
+        return aggregate_for32(d_delta, d_base, len, blocks, agg_mask, d_out, d_ws, ws_bytes, stream);
+    }
+    if (!d_out || !d_ws) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32_expr: NULL argument");
+    if (len < 0) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32_expr: negative length");
+    if (ws_bytes < kPartialsBytes) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32_expr: workspace too small");
+    if (agg_mask & ~(uint32_t)(FQ_AGG_MIN | FQ_AGG_MAX | FQ_AGG_SUM | FQ_AGG_COUNT))
+        return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32_expr: unknown bits in agg_mask");
+    if (((uintptr_t)d_delta) % 16)
+        return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32_expr: delta not aligned to 16 bytes");
+    if (((uintptr_t)d_base) % 8) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32_expr: base not aligned to 8 bytes");
+    if (len > 0 && (!d_delta || !d_base)) return fqc::fail(FQ_E_INVALID, "fq_aggregate_for32_expr: NULL argument");
+    Launch L;
+    bool chain = false;
+    uint64_t blocks = 0;
+    int empty_if_zero = 0;
+    fq_status s = plan_scan_for32(d_delta, d_base, len, block_rows, pred, value, agg_mask, true, L, chain, blocks,
+                                  empty_if_zero);
+    if (s != FQ_OK) return s;
+    L.stream = (hipStream_t)stream;
+    L.parts = (Partial *)d_ws;
+    bool jitted = false;
+    s = jit_scan(FQ_DT_UINT64, chain, L, &jitted, true);  // no interpreting kernel knows the deltas
+    if (s != FQ_OK) return s;
+    if (!jitted) return fqc::fail(FQ_E_UNSUPPORTED, kFor32NeedsJit);
+    return dispatch_finalize(L, blocks, empty_if_zero, d_out);
+}
+
+fq_status fq_jit_prepare_for32(int64_t len, int64_t block_rows, const fq_pred *pred, const fq_expr *value,
+                               uint32_t agg_mask, int32_t *specialised) {
+    using namespace fqk;
+    if (specialised) *specialised = 0;
+    if (len < 0) return fqc::fail(FQ_E_INVALID, "fq_jit_prepare_for32: negative length");
+    if (agg_mask & ~(uint32_t)(FQ_AGG_MIN | FQ_AGG_MAX | FQ_AGG_SUM | FQ_AGG_COUNT))
+        return fqc::fail(FQ_E_INVALID, "fq_jit_prepare_for32: unknown bits in agg_mask");
+    if (for32_identity(pred, value)) return FQ_OK;  // the precompiled agg_flat_kernel_for32
+    Launch L;
+    bool chain = false;
+    uint64_t blocks = 0;
+    int empty_if_zero = 0;
+    fq_status s = plan_scan_for32(nullptr, nullptr, len, block_rows, pred, value, agg_mask, false, L, chain, blocks,
+                                  empty_if_zero);
+    if (s != FQ_OK) return s;
+    bool ok = false;
+    s = jit_prepare(FQ_DT_UINT64, chain, L, &ok);
+    if (s != FQ_OK) return s;
+    if (!ok) return fqc::fail(FQ_E_UNSUPPORTED, kFor32NeedsJit);
+    if (specialised) *specialised = 1;
+    return FQ_OK;
 }
 
 fq_status fq_jit_prepare(const fq_col *col, int64_t block_rows, const fq_pred *pred, const fq_expr *value,

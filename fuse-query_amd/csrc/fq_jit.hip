@@ -296,6 +296,7 @@ std::string shape_key(const Launch &L, int32_t tin, bool chain, int dev) {
     std::string k;
     k.reserve(256);
     auto put = [&k](int32_t v) { k.append(reinterpret_cast<const char *>(&v), sizeof v); };
+    if (L.for32) put(-32);  // fq_jit_scan_for32: where a plain key has its device (>= -1)
     put(dev);
     put(block_mode_vectors());
     put(tin);
@@ -722,6 +723,134 @@ void gen_cols_loop(const Launch &L, int K, std::string &src) {
            "    }\n";
 }
 
+// The loops of fq_jit_scan_for32 (fq_aggregate_for32_expr): one UInt64 column
+// read as its 32-bit deltas, a row being fbase[row >> 16] + delta[row].
+// Flat: agg_flat_kernel_for32's tiles (4 16-byte vectors of 4 deltas per lane,
+// 16 whole tiles to a frame) with the next tile's loads in flight as in
+// fq_jit_scan; the frame base is the CURRENT tile's (the prefetched tile lies
+// in another frame as soon as the grid has 16 workgroups), workgroup-uniform,
+// one load per tile.  Vectors past the last whole tile and the up to 3 rows
+// after them look their base up from the row index.
+// Block mode: one wave per reference block and one ballot per block.  A block
+// starts on a 16-byte boundary of delta iff R % 4 == 0; a 4-row vector at a row
+// that is a multiple of 4 never straddles a frame, but a block may (blocks of
+// 10,000 rows do not divide a frame), so the base is looked up per vector
+// (two bases per iteration of the wave's loop, loaded once and chosen by the
+// row, with the dead vector steps of a block's last iteration skipped, measured
+// slower: DESIGN.md section 3).  Any other R reads 4-byte elements with the
+// base per row.
+void gen_for32_loop(const Launch &L, std::string &src) {
+    const std::string SH = std::to_string(kFor32FrameShift);
+    const std::string TPF = std::to_string(kFor32FrameShift - 12);  // log2(tiles per frame): tiles of 2^12 rows
+    static_assert(kFor32TileRows == 4096, "t >> (shift - 12) is the tile's frame");
+    if (!L.block_mode) {
+        src += R"(
+    (void)R;
+    const long long T = (long long)gridDim.x * 256;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long nvec = n / 4;
+    const u32x4 *__restrict__ vp = (const u32x4 *)delta;
+    const long long TV = 4 * 256;
+    const long long ntiles = nvec / TV;
+    // next tile's loads in flight while this tile is evaluated
+    u32x4 nxt[4];
+    if ((long long)blockIdx.x < ntiles) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            nxt[k] = __builtin_nontemporal_load(vp + (long long)blockIdx.x * TV + threadIdx.x + (long long)k * 256);
+    }
+    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const long long v0 = t * TV + threadIdx.x;
+        u32x4 raw[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) raw[k] = nxt[k];
+        const long long tn = t + gridDim.x;
+        if (tn < ntiles) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) nxt[k] = __builtin_nontemporal_load(vp + tn * TV + threadIdx.x + (long long)k * 256);
+        }
+        const u64 fb = fbase[t >> )" + TPF + R"(];  // this tile's frame, not the prefetched one's
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            u32 d[4];
+            __builtin_memcpy(&d[0], &raw[k], 16);
+            const long long i0 = (v0 + (long long)k * 256) * 4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) fq_acc(acc, fb + (u64)d[j], i0 + j, 1u, c, bitmap);
+        }
+    }
+    for (long long v = ntiles * TV + g; v < nvec; v += T) {
+        const u32x4 raw = __builtin_nontemporal_load(vp + v);
+        const u64 fb = fbase[(v * 4) >> )" + SH + R"(];  // a 4-row vector never straddles a frame
+        u32 d[4];
+        __builtin_memcpy(&d[0], &raw, 16);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fq_acc(acc, fb + (u64)d[j], v * 4 + j, 1u, c, bitmap);
+    }
+    for (long long i = nvec * 4 + g; i < n; i += T) fq_acc(acc, fbase[i >> )" + SH + R"(] + (u64)delta[i], i, 1u, c, bitmap);
+)";
+        return;
+    }
+    src += R"(
+    const int lane = threadIdx.x & 63;
+    const long long w = ((long long)blockIdx.x * 256 + threadIdx.x) / 64;
+    const long long W = ((long long)gridDim.x * 256) / 64;
+    const long long nb = (n + R - 1) / R;
+    const bool vec = (R & 3) == 0;
+    for (long long b = w; b < nb; b += W) {
+        const long long s = b * R;
+        const long long e = (s + R < n) ? s + R : n;
+        u32 any = 0;
+        if (vec) {
+            const long long nv = (e - s) >> 2;
+            const u32x4 *__restrict__ bp = (const u32x4 *)(delta + s);
+            for (long long v = lane; v < nv; v += 64 * BM_U) {
+                u32x4 raw[BM_U];
+                u64 fb[BM_U];
+#pragma unroll
+                for (int k = 0; k < BM_U; ++k) {
+                    const long long vk = v + (long long)k * 64;
+                    if (vk < nv) {
+                        raw[k] = __builtin_nontemporal_load(bp + vk);
+                        fb[k] = fbase[(s + 4 * vk) >> )" + SH + R"(];  // the base may change inside a block
+                    } else {
+                        raw[k] = u32x4{0u, 0u, 0u, 0u};
+                        fb[k] = 0ull;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < BM_U; ++k) {
+                    const long long vk = v + (long long)k * 64;
+                    const u32 li = vk < nv ? 1u : 0u;
+                    u32 d[4];
+                    __builtin_memcpy(&d[0], &raw[k], 16);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) any |= fq_acc(acc, fb[k] + (u64)d[j], s + 4 * vk + j, li, c, bitmap);
+                }
+            }
+            const long long r = s + 4 * nv + lane;  // the last block's up to 3 rows after its vectors
+            if (r < e) any |= fq_acc(acc, fbase[r >> )" + SH + R"(] + (u64)delta[r], r, 1u, c, bitmap);
+            if (__ballot(any != 0) == 0ull) acc.flags |= )" + std::to_string(FQ_STATE_ANY_EMPTY) + R"(u;
+            continue;
+        }
+        for (long long i = s + lane; i < e; i += 64 * 8) {
+            TIn x[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const long long ik = i + (long long)k * 64;
+                x[k] = ik < e ? fbase[ik >> )" + SH + R"(] + (u64)__builtin_nontemporal_load(delta + ik) : TIn(0);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const long long ik = i + (long long)k * 64;
+                any |= fq_acc(acc, x[k], ik, ik < e ? 1u : 0u, c, bitmap);
+            }
+        }
+        if (__ballot(any != 0) == 0ull) acc.flags |= )" + std::to_string(FQ_STATE_ANY_EMPTY) + R"(u;
+    }
+)";
+}
+
 // Full kernel source for one shape.  Returns false if the shape is outside
 // what the generator handles (the caller then interprets).
 bool gen_source(const Launch &L, int32_t tin, bool chain, Gen &g, std::string &src) {
@@ -830,11 +959,18 @@ __device__ __forceinline__ Partial wg_reduce(Acc acc) {
         for (int j = 0; j < K; ++j)
             cols_params += (j ? ", const TIn" : "const TIn") + std::to_string(j) + " *__restrict__ col" + std::to_string(j);
     }
-    src += "extern \"C\" __global__ void __launch_bounds__(256)\n"
-           "fq_jit_scan(" + cols_params + ", long long n, long long head, long long R,\n"
-           "            const u64 *__restrict__ bitmap, Consts c, Partial *parts) {\n"
-           "    Acc acc;\n    acc.sum = V(0); acc.mx = " + lo + "; acc.mn = " + hi + "; acc.cnt = 0; acc.flags = 0;\n";
-    if (K) {
+    if (L.for32)
+        src += "extern \"C\" __global__ void __launch_bounds__(256)\n"
+               "fq_jit_scan_for32(const u32 *__restrict__ delta, const u64 *__restrict__ fbase, long long n, long long R,\n"
+               "                  const u64 *__restrict__ bitmap, Consts c, Partial *parts) {\n";
+    else
+        src += "extern \"C\" __global__ void __launch_bounds__(256)\n"
+               "fq_jit_scan(" + cols_params + ", long long n, long long head, long long R,\n"
+               "            const u64 *__restrict__ bitmap, Consts c, Partial *parts) {\n";
+    src += "    Acc acc;\n    acc.sum = V(0); acc.mx = " + lo + "; acc.mn = " + hi + "; acc.cnt = 0; acc.flags = 0;\n";
+    if (L.for32) {
+        gen_for32_loop(L, src);
+    } else if (K) {
         gen_cols_loop(L, K, src);
     } else if (!L.block_mode) {
         // flat tile-contiguous streaming (agg_flat_kernel, U = 4 16-byte vectors per lane)
@@ -4509,7 +4645,7 @@ fq_status get_kernel(int32_t col_dtype, bool chain, const Launch &L, hipFunction
         std::string src;
         Compiled c;
         if (L.typed ? gen_typed_source(L, chain, src) : gen_source(L, col_dtype, chain, g, src)) {
-            fq_status s = compile(src, dev, c);
+            fq_status s = compile(src, dev, c, L.for32 ? "fq_jit_scan_for32" : "fq_jit_scan");
             if (s != FQ_OK) return s;
             c.ok = true;
         }
@@ -4574,6 +4710,14 @@ fq_status jit_scan(int32_t col_dtype, bool chain, const Launch &L, bool *used, b
         args[na++] = &bitmap;
         args[na++] = &hc;
         args[na++] = &parts;
+        FQ_HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)L.grid, 1, 1, kThreads, 1, 1, 0, L.stream, args, nullptr));
+        g_jit_launches += 1;
+        *used = true;
+        return FQ_OK;
+    }
+    if (L.for32) {  // fq_jit_scan_for32(delta, fbase, n, R, ...)
+        const uint64_t *fbase = L.for32_base;
+        void *args[] = {&col, &fbase, &n, &R, &bitmap, &hc, &parts};
         FQ_HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)L.grid, 1, 1, kThreads, 1, 1, 0, L.stream, args, nullptr));
         g_jit_launches += 1;
         *used = true;

@@ -51,7 +51,26 @@ struct Launch {
     bool nullable;
     bool has_bm[FQ_MAX_SCAN_COLS];
     const uint64_t *validity[FQ_MAX_SCAN_COLS];
+    // fq_aggregate_for32_expr: one UInt64 column given as its 32-bit deltas
+    // (`col`, 16-byte aligned) and frame bases; a kernel and a shape key of its
+    // own (fq_jit_scan_for32), grid as fq_aggregate_for32 in flat mode
+    bool for32;
+    const uint64_t *for32_base;
 };
+
+// Geometry of the scans over a frame-of-reference copy (fq_aggregate_for32,
+// fq_jit_scan_for32): a tile is 4 16-byte vectors of 4 deltas per lane, and 16
+// whole tiles make a frame, so a tile never straddles one.
+constexpr int kFor32FrameShift = 16;  // log2(FQ_FOR32_FRAME_ROWS)
+constexpr int64_t kFor32TileRows = 4 * kThreads * 4;
+static_assert(((int64_t)1 << kFor32FrameShift) == FQ_FOR32_FRAME_ROWS, "row >> kFor32FrameShift is the frame");
+static_assert(FQ_FOR32_FRAME_ROWS % kFor32TileRows == 0, "a tile never straddles a frame");
+// workgroups of a flat scan over `len` deltas (flat_max = CUs x FQ_TUNE_SCAN_WG_PER_CU)
+inline int for32_flat_grid(int64_t len, int64_t flat_max) {
+    int64_t grid = (len / 4 + kFor32TileRows / 4 - 1) / (kFor32TileRows / 4);
+    if (grid < 1) grid = 1;
+    return (int)(grid < flat_max ? grid : flat_max);
+}
 
 // Row group of a typed scan over columns of the given widths: the largest
 // power of two G <= 16 with G * sum(w) <= 64 bytes per lane, so that a tile and

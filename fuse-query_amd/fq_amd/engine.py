@@ -10,6 +10,7 @@ Projection / Limit) on the gfx950 kernels.
 """
 import ctypes as C
 import gc
+import os
 
 import numpy as np
 
@@ -22,6 +23,7 @@ P = C.POINTER
 OPT_WORKER_THREADS, OPT_MODULO, OPT_PROFILE, OPT_STREAMS, OPT_CHUNK_ROWS, OPT_GROUP_CHUNK_ROWS = 1, 2, 3, 4, 5, 6
 OPT_FAULT_PIPE = 7  # testing: merged pipe k (1-based) fails its device-context setup
 OPT_RESIDENT_FOR32 = 8  # 1: resident partitions also kept, and scanned, as per-frame 32-bit deltas (Engine's default)
+OPT_RESIDENT_FOR32_FUSED = 9  # 1 (with option 8): fused WHERE / expression scans read the delta copies too
 PROFILE_PAIRS, PROFILE_SPAN = 1, 2  # FQ_OPT_PROFILE values
 
 ENGINE_SYMBOLS = [
@@ -251,7 +253,8 @@ class BlockStream:
 
 
 class Engine:
-    def __init__(self, device=0, worker_threads=8, modulo=True, profile=False, streams=1, resident_for32=True):
+    def __init__(self, device=0, worker_threads=8, modulo=True, profile=False, streams=1, resident_for32=True,
+                 for32_fused=None):
         import weakref
         self._streams = weakref.WeakSet()  # open BlockStreams
         h = C.c_void_p()
@@ -266,6 +269,11 @@ class Engine:
         # resident partitions also kept, and scanned, as 32-bit deltas (fq_engine.h); None: the library's default (off)
         if resident_for32 is not None:
             self.set_option(OPT_RESIDENT_FOR32, 1 if resident_for32 else 0)
+        # scans with a fused WHERE / argument expression read the delta copies too (fq_engine.h); None: from
+        # the environment (FQ_RESIDENT_FOR32_FUSED=1 turns it on), otherwise off
+        if for32_fused is None:
+            for32_fused = os.environ.get("FQ_RESIDENT_FOR32_FUSED") == "1"
+        self.set_option(OPT_RESIDENT_FOR32_FUSED, 1 if for32_fused else 0)
 
     def set_option(self, opt, value):
         check(lib.fq_engine_set_option(self.h, opt, int(value)))

@@ -299,6 +299,19 @@ def aggregate_for32(enc, mask=0xF, ws=None, stream=None):
     return state_from_device(out)
 
 
+def aggregate_for32_expr(enc, block_rows=0, pred=None, value=None, mask=0xF, ws=None, stream=None):
+    """fq_aggregate_for32_expr over a For32Column: fq_aggregate over the column it
+    stands for, read as 4-byte deltas -> host fq_agg_state."""
+    require_gpu()
+    ws = ws or Workspace(lib.fq_aggregate_workspace_bytes(enc.len))
+    out = torch.empty(48, dtype=torch.uint8, device="cuda")
+    check(lib.fq_aggregate_for32_expr(C.c_void_p(enc.delta.ptr), C.c_void_p(enc.base.ptr), enc.len, int(block_rows),
+                                      C.byref(pred) if pred is not None else None,
+                                      C.byref(value) if value is not None else None, mask,
+                                      C.c_void_p(out.data_ptr()), ws.ptr, ws.nbytes, _stream(stream)))
+    return state_from_device(out)
+
+
 def state_values(st):
     """fq_agg_state -> dict(sum, max, min, count, blocks, flags) of Python values;
     fq_agg_state_n: also `valid`, and sum / max / min are None when valid == 0."""
@@ -670,6 +683,15 @@ def jit_prepare(dtype, pred=None, value=None, mask=abi.AGG_SUM, block_rows=0, le
     out = C.c_int32(0)
     check(lib.fq_jit_prepare(C.byref(c), int(block_rows), C.byref(pred) if pred is not None else None,
                              C.byref(value) if value is not None else None, mask, C.byref(out)))
+    return bool(out.value)
+
+
+def jit_prepare_for32(pred=None, value=None, mask=abi.AGG_SUM, block_rows=0, length=1 << 30):
+    """jit_prepare for fq_aggregate_for32_expr (a UInt64 column as 32-bit deltas).
+    False for the call without predicate and expression: its kernel is precompiled."""
+    out = C.c_int32(0)
+    check(lib.fq_jit_prepare_for32(int(length), int(block_rows), C.byref(pred) if pred is not None else None,
+                                   C.byref(value) if value is not None else None, mask, C.byref(out)))
     return bool(out.value)
 
 

@@ -74,6 +74,17 @@ typedef struct fq_result fq_result;
                                    is 0: a host that sized its HBM for 8 B per resident row, or reads
                                    scan_bytes as 8 B per row, sees no change until it opts in.  The
                                    Python binding (fq_amd.engine.Engine) opts in by default */
+#define FQ_OPT_RESIDENT_FOR32_FUSED 9 /* 1, with FQ_OPT_RESIDENT_FOR32 = 1: a fused aggregate scan of one
+                                   resident UInt64 column WITH a fused WHERE and/or an argument
+                                   expression (`max(number+1) WHERE number%8<3`) reads the delta copy
+                                   too (fq_aggregate_for32_expr; scan_bytes counts 4 B per row and 8 B
+                                   per frame), wherever the JIT would specialise the scan: FQ_JIT_ALWAYS,
+                                   or FQ_JIT_AUTO with at least min_rows rows, and hipRTC loadable --
+                                   the interpreting kernels know no deltas, so any other scan reads the
+                                   plain column as before.  Slices, GROUP BY, Filter -> Projection and
+                                   the unfused path read the plain column.  0 (the default, also of the
+                                   Python binding unless FQ_RESIDENT_FOR32_FUSED=1 is in the
+                                   environment): such scans read 8 B per row */
 
 typedef struct fq_engine_stats {
     uint64_t scan_launches; /* fused aggregate scans launched                    */

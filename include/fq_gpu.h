@@ -371,7 +371,22 @@ fq_status fq_jit_prepare_nullable(const fq_col *cols, const uint8_t *has_validit
  * (wrapping sum, max, min, count, flags 0, dtype UInt64), from 4 bytes per row
  * read.  Workspace and the fixed-order fold are fq_aggregate's; a request for
  * count alone reads nothing.  FQ_E_INVALID for a delta pointer that is not
- * 16-byte aligned or unknown bits in agg_mask.                              */
+ * 16-byte aligned or unknown bits in agg_mask.
+ *
+ * fq_aggregate_for32_expr is fq_aggregate over the UInt64 column
+ * base[i / FQ_FOR32_FRAME_ROWS] + delta[i] with the same block_rows, pred,
+ * value and agg_mask: the same fq_agg_state (integer sum, max, min and count,
+ * blocks, flags and dtype bit for bit; a Float64 max/min bit for bit up to the
+ * sign of a zero extreme; a Float64 sum bit for bit wherever it is exactly
+ * summable -- a lane owns other rows here than in the plain scan), and the same
+ * error order.  Without predicate and expression the call is
+ * fq_aggregate_for32 (over block_rows' blocks).  Any other shape runs on a
+ * hipRTC-specialised kernel of its own (fq_jit_scan_for32) whatever min_rows
+ * says: FQ_E_UNSUPPORTED with FQ_JIT_OFF or without hipRTC.  Argument errors
+ * are fq_aggregate_for32's.  fq_jit_prepare_for32 compiles that kernel ahead
+ * of the first scan (*specialised = 0 for the call without predicate and
+ * expression, whose kernel is precompiled); without a GPU the source is
+ * compiled for gfx950 only to validate it.                                  */
 #define FQ_FOR32_FRAME_ROWS 65536
 int64_t fq_for32_frames(int64_t len);
 size_t fq_for32_delta_bytes(int64_t len);
@@ -379,6 +394,11 @@ size_t fq_for32_base_bytes(int64_t len);
 fq_status fq_for32_encode(const fq_col *col, uint64_t *d_base, uint32_t *d_delta, uint32_t *d_flag, void *stream);
 fq_status fq_aggregate_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t len, uint32_t agg_mask,
                              fq_agg_state *d_out, void *d_ws, size_t ws_bytes, void *stream);
+fq_status fq_aggregate_for32_expr(const uint32_t *d_delta, const uint64_t *d_base, int64_t len, int64_t block_rows,
+                                  const fq_pred *pred, const fq_expr *value, uint32_t agg_mask, fq_agg_state *d_out,
+                                  void *d_ws, size_t ws_bytes, void *stream);
+fq_status fq_jit_prepare_for32(int64_t len, int64_t block_rows, const fq_pred *pred, const fq_expr *value,
+                               uint32_t agg_mask, int32_t *specialised);
 
 /* ---- ArithmeticFunction::eval (data_array_arithmetic.rs:14-55) ----
  * Exactly one of {lhs, lhs_scalar} and one of {rhs, rhs_scalar} is non-NULL.

@@ -154,8 +154,11 @@ __global__ void __launch_bounds__(256)
         bool ok = true;
         const TC a = lsc ? lconst : load_as<TC>(l, ldt, i, ok);
         const TC b = rsc ? rconst : load_as<TC>(r, rdt, i, ok);
-        if (!ok) flags |= FQ_STATE_CAST_NULL;
-        out[i] = arith<TC>(op, a, b, flags);
+        // arrow's divide checks valid rows only: a row whose cast is null (load_as still
+        // returns its truncation, which may be 0) raises no Divide by zero
+        uint32_t row = 0;
+        out[i] = arith<TC>(op, a, b, row);
+        flags |= ok ? row : (uint32_t)FQ_STATE_CAST_NULL;
     }
     flush_flags(flags, flag);
 }

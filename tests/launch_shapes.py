@@ -223,6 +223,32 @@ def ew_compare(cus, ew_wg_per_cu):
 
 
 # ---------------------------------------------------------------------------
+# the generic element-wise kernels (any type pair, any alignment) and fq_logic
+# (line numbers of the commit that added these three models)
+# ---------------------------------------------------------------------------
+def ew_arith_generic(cus):
+    """arith_kernel<TC>: one row per thread and round of the grid-stride loop"""
+    # fq_elementwise.hip:420-423 (prepare)  max_grid = cus * 8; grid = max(1, min(ceil(n / 256), max_grid))
+    # fq_elementwise.hip:150, :153 (arith_kernel)  T = gridDim.x * 256 rows per round; row i -> thread i % T
+    return Model("ew_arith_generic", THREADS, cus * 8, True, True)
+
+
+def ew_compare_generic(cus):
+    """compare_kernel<TC>: one 64-row bitmap word per wave and round, four per workgroup"""
+    # fq_elementwise.hip:542-545 (fq_compare)  nwords = ceil(len / 64); grid = min(ceil(nwords / 4), cus * 8)
+    # fq_elementwise.hip:174, :177 (compare_kernel)  W = gridDim.x * 256 / 64 words per round; word w -> wave w % W
+    return Model("ew_compare_generic", WAVES * 64, cus * 8, True, True)
+
+
+def ew_logic(cus):
+    """logic_kernel: one pair of bitmap words (16 bytes) per thread and round; an odd last word to the scalar loop"""
+    # fq_elementwise.hip:605-609 (fq_logic)  nwords = ceil(len / 64); grid = max(1, min(ceil((nwords / 2) / 256), cus * 2))
+    # fq_elementwise.hip:567-568, :576 (logic_kernel)  T = gridDim.x * 256 pairs per round; pair p -> thread p % T
+    # (the grid counts whole pairs, so the cap is its upper bound: one word past k * 512 still gives k workgroups)
+    return Model("ew_logic", THREADS * 2 * 64, cus * 2, True, False)
+
+
+# ---------------------------------------------------------------------------
 # fq_filter_compact: no capped grid (fq_filter.hip:1128-1132, fq_filter_compact: one workgroup per group of kGroupTiles = 16 tiles
 # of kTileWords = 256 bitmap words, one scatter workgroup per tile), so only these sizes matter
 # ---------------------------------------------------------------------------

@@ -84,6 +84,13 @@ fq_status filter_project_blocks_enqueue_typed(const fq_col *cols, int32_t n_cols
                                               void *const *d_out, int64_t *d_counts, uint64_t *h_result,
                                               uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
                                               void *ev_end, void *stream);
+// the same for fq_filter_project_blocks_for32: rows [first, first + len) of the
+// UInt64 column encoded as d_delta / d_base
+fq_status filter_project_blocks_enqueue_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t first,
+                                              int64_t len, int64_t block_rows, const fq_pred *pred,
+                                              const fq_expr *values, int32_t n_out, void *const *d_out,
+                                              int64_t *d_counts, uint64_t *h_result, uint64_t *d_result, void *d_ws,
+                                              size_t ws_bytes, void *ev_start, void *ev_end, void *stream);
 fq_status filter_project_blocks_result(const uint64_t *h_result, int64_t *out_len);
 // Whether the typed projection's lowering takes this predicate and these
 // values over columns of dtypes cdt: the dry run of typed_scan_fits for

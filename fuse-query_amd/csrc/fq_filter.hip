@@ -744,14 +744,24 @@ size_t fq_filter_project_blocks_workspace_bytes(void) { return 3 * sizeof(uint64
 
 namespace fqk {
 
+// a window of a frame-of-reference copy (fq_filter_project_blocks_for32): the
+// encoded column's bases and the window's first row in it; the column passed
+// beside it holds the deltas' own start and the window's length
+struct For32Window {
+    const uint64_t *base;
+    int64_t first;
+};
+
 // typed: the call of fq_filter_project_blocks_typed with a narrow type in it (its columns checked)
+// win: the call of fq_filter_project_blocks_for32 (one UInt64 column, its arguments checked)
 static fq_status blocks_enqueue(bool typed, const fq_col *cols, int32_t n_cols, int64_t block_rows,
                                 const fq_pred *pred, const fq_expr *values, int32_t n_out,
                                 void *const *d_out, int64_t *d_counts, uint64_t *h_result,
                                 uint64_t *d_result, void *d_ws, size_t ws_bytes, void *ev_start,
-                                void *ev_end, void *stream) {
-    const std::string who = typed ? "fq_filter_project_blocks_typed"
-                                  : n_cols > 1 ? "fq_filter_project_blocks_columns" : "fq_filter_project_blocks";
+                                void *ev_end, void *stream, const For32Window *win = nullptr) {
+    const std::string who = win     ? "fq_filter_project_blocks_for32"
+                            : typed ? "fq_filter_project_blocks_typed"
+                                    : n_cols > 1 ? "fq_filter_project_blocks_columns" : "fq_filter_project_blocks";
     static_assert(FQ_PROJECT_MIN_BLOCK_ROWS == kProjectBlockTile, "the ABI's minimum block is the kernel's tile");
     if (!h_result) return fqc::fail(FQ_E_INVALID, who + ": NULL result words");
     // a resident call's words are the caller's until the hand-off writes them
@@ -773,6 +783,13 @@ static fq_status blocks_enqueue(bool typed, const fq_col *cols, int32_t n_cols, 
     if (s != FQ_OK) return s;
     const fq_col *col = cols;
     if (n_out < 1) return fqc::fail(FQ_E_INVALID, who + ": no outputs");
+    if (win) {
+        if (P.pred.kind == FQ_PRED_NONE)
+            return fqc::fail(FQ_E_UNSUPPORTED, who + ": no predicate (the map kernel reads the plain column)");
+        P.for32 = true;
+        P.for32_base = win->base;
+        P.for32_first = win->first;
+    }
     if (!jit_project_available())
         return fqc::fail(FQ_E_UNSUPPORTED, who + ": hipRTC unavailable or the JIT is off");
     if ((s = jit_project_prepare(col->dtype, P)) != FQ_OK) return s;
@@ -850,6 +867,33 @@ fq_status filter_project_blocks_enqueue(const fq_col *col, int64_t block_rows, c
                                                  d_result, d_ws, ws_bytes, ev_start, ev_end, stream);
 }
 
+fq_status filter_project_blocks_enqueue_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t first,
+                                              int64_t len, int64_t block_rows, const fq_pred *pred,
+                                              const fq_expr *values, int32_t n_out, void *const *d_out,
+                                              int64_t *d_counts, uint64_t *h_result, uint64_t *d_result, void *d_ws,
+                                              size_t ws_bytes, void *ev_start, void *ev_end, void *stream) {
+    if (!h_result) return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks_for32: NULL result words");
+    const char *bad = first < 0                             ? "negative first row"
+                      : len < 0                             ? "negative length"
+                      : first > INT64_MAX - len             ? "first + len overflows"
+                      : len > 0 && (!d_delta || !d_base)    ? "NULL deltas or bases"
+                      : len > 0 && !d_counts                ? "NULL block counts"
+                      : block_rows < FQ_PROJECT_MIN_BLOCK_ROWS ? "block_rows below FQ_PROJECT_MIN_BLOCK_ROWS"
+                                                            : nullptr;
+    if (bad) {
+        if (h_result && !d_result) h_result[0] = h_result[1] = 0;
+        return fqc::fail(FQ_E_INVALID, std::string("fq_filter_project_blocks_for32: ") + bad);
+    }
+    if (((uintptr_t)d_delta & 3u) || ((uintptr_t)d_base & 7u)) {
+        if (h_result && !d_result) h_result[0] = h_result[1] = 0;
+        return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks_for32: deltas or bases not aligned to their element");
+    }
+    const fq_col col{(void *)d_delta, len, FQ_DT_UINT64, 0};  // the deltas' start; the rows are UInt64
+    const For32Window win{d_base, first};
+    return blocks_enqueue(false, &col, 1, block_rows, pred, values, n_out, d_out, d_counts, h_result, d_result, d_ws,
+                          ws_bytes, ev_start, ev_end, stream, &win);
+}
+
 bool typed_project_fits(const int32_t *cdt, int32_t n_cols, const fq_pred *pred, const fq_expr *values, int32_t n_out) {
     if (!cdt || n_cols < 1 || n_cols > FQ_MAX_SCAN_COLS || n_out < 0 || n_out > FQ_MAX_PROJECT || (n_out > 0 && !values))
         return false;
@@ -914,6 +958,46 @@ fq_status fq_filter_project_blocks_columns(const fq_col *cols, int32_t n_cols, i
     if (s != FQ_OK) return s;
     FQ_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return filter_project_blocks_result(host, out_len);
+}
+
+fq_status fq_filter_project_blocks_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t first, int64_t len,
+                                         int64_t block_rows, const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                         void *const *d_out, int64_t *d_counts, int64_t *out_len, void *d_ws,
+                                         size_t ws_bytes, void *stream) {
+    if (!out_len) return fqc::fail(FQ_E_INVALID, "fq_filter_project_blocks_for32: NULL out_len");
+    *out_len = 0;
+    uint64_t local[2] = {0, 0};
+    uint64_t *const pinned = fqc::host_staging();
+    uint64_t *const host = pinned ? pinned : local;  // kept rows, flag words
+    fq_status s = fqk::filter_project_blocks_enqueue_for32(d_delta, d_base, first, len, block_rows, pred, values, n_out,
+                                                           d_out, d_counts, host, nullptr, d_ws, ws_bytes, nullptr,
+                                                           nullptr, stream);
+    if (s != FQ_OK) return s;
+    FQ_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return fqk::filter_project_blocks_result(host, out_len);
+}
+
+fq_status fq_jit_prepare_project_for32(int64_t block_rows, const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                       int32_t *specialised) {
+    using namespace fqk;
+    if (specialised) *specialised = 0;
+    if (block_rows < FQ_PROJECT_MIN_BLOCK_ROWS)
+        return fqc::fail(FQ_E_INVALID, "fq_jit_prepare_project_for32: block_rows below FQ_PROJECT_MIN_BLOCK_ROWS");
+    if (n_out < 1 || n_out > FQ_MAX_PROJECT)
+        return fqc::fail(FQ_E_INVALID, "fq_jit_prepare_project_for32: n_out must be 1.." + std::to_string(FQ_MAX_PROJECT) +
+                                           ", got " + std::to_string(n_out));
+    const fq_col c0{nullptr, 0, FQ_DT_UINT64, 0};  // the shape only: no buffers needed
+    void *none[FQ_MAX_PROJECT] = {};
+    ProjLaunch P;
+    fq_status s = lower_projection(&c0, pred, values, n_out, none, nullptr, P);
+    if (s != FQ_OK) return s;
+    if (P.pred.kind == FQ_PRED_NONE)
+        return fqc::fail(FQ_E_UNSUPPORTED, "fq_jit_prepare_project_for32: no predicate (the map kernel reads the plain column)");
+    if (!jit_project_available()) return FQ_OK;  // the caller's plain path answers
+    P.for32 = true;
+    if ((s = jit_project_prepare(FQ_DT_UINT64, P)) != FQ_OK) return s;
+    if (specialised) *specialised = 1;
+    return FQ_OK;
 }
 
 size_t fq_blocks_compact_workspace_bytes(int64_t n_blocks) {

@@ -3256,6 +3256,7 @@ std::string proj_shape_key(const ProjLaunch &P, int32_t tin, int dev) {
     std::string k = "PROJb" + std::to_string(fqc::knob(FQ_TUNE_SELECT_BLOCKS_ROWS)) + "S" +
                     std::to_string(fqc::knob(FQ_TUNE_SELECT_BLOCKS_STAGE));
     auto put = [&k](int32_t v) { k.append(reinterpret_cast<const char *>(&v), sizeof v); };
+    if (P.for32) put(-32);  // fq_jit_pblocks_for32: where a plain key has its device (>= -1)
     put(dev);
     put(tin);
     put_pred_key(P.pred, k);
@@ -3485,7 +3486,7 @@ fq_jit_pblocks()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, lon
     return s;
 }
 
-std::string gen_project_blocks_kernel(const ProjLaunch &P, int K) {
+std::string gen_project_blocks_kernel(const ProjLaunch &P, int K, bool for32 = false) {
     const bool bitmap_pred = P.pred.kind == FQ_PRED_BITMAP;
     // several columns: project_cols_rows(K) rows per thread and a whole-tile stage of one output
     std::string s = "#define PB_ROWS " + std::to_string(K > 1 ? project_cols_rows(K) : fqc::knob(FQ_TUNE_SELECT_BLOCKS_ROWS)) +
@@ -3551,9 +3552,16 @@ __device__ __forceinline__ void pb_copy(const TIn *__restrict__ st, u32 base, u3
 }
 #endif
 )";
-    s += R"(extern "C" __global__ void __launch_bounds__(PB_THREADS)
+    // fq_jit_pblocks_for32: the column as per-frame 32-bit deltas (fq_for32_encode),
+    // rows [first, first + n) of it; only the signature and the load phase differ
+    s += for32 ? R"(extern "C" __global__ void __launch_bounds__(PB_THREADS)
+fq_jit_pblocks_for32(const u32 *__restrict__ delta, const u64 *__restrict__ fbase, long long first, long long n,
+    long long B, Consts c,
+)"
+               : R"(extern "C" __global__ void __launch_bounds__(PB_THREADS)
 fq_jit_pblocks(const TIn *__restrict__ col, long long n, long long B, Consts c,
-    const u64 *__restrict__ bm, Outs o, long long *__restrict__ counts, u32 *__restrict__ fl,
+)";
+    s += R"(    const u64 *__restrict__ bm, Outs o, long long *__restrict__ counts, u32 *__restrict__ fl,
     unsigned long long *__restrict__ total, u32 *__restrict__ ticket, int al) {
     __shared__ PbShared sh;
 #if PB_STAGE
@@ -3590,7 +3598,41 @@ fq_jit_pblocks(const TIn *__restrict__ col, long long n, long long B, Consts c,
         u64 *__restrict__ b0s = sh.b0[par];
         u64 *__restrict__ b1s = sh.b1[par];
         u32 *__restrict__ off = sh.off[par];
-        // 16-byte row-pair loads when the tile is whole and 16-byte aligned
+)";
+    // The tile's rows into x0 / x1.  Over deltas: row r is fbase[(first + r) >> 16]
+    // + delta[first + r].  A tile is at most one frame long, so it meets at most
+    // one frame edge: two workgroup-uniform bases, fb_lo of the tile's first row
+    // and fb_hi of its last (clamped to the window's last row: fbase holds no
+    // word past the encoded column's last frame), chosen per row -- with an odd
+    // first or an odd B a pair straddles the edge.
+    s += for32 ? R"(        const long long g0 = first + r0;                // the tile's first row in the encoded column
+        const long long fe = ((g0 >> 16) + 1) << 16;  // the first row of the frame after g0's
+        const long long f_hi = (g0 + PB_TILE - 1) >> 16, f_last = (first + end - 1) >> 16;
+        const u64 fb_lo = fbase[g0 >> 16], fb_hi = fbase[f_hi < f_last ? f_hi : f_last];
+        const u32 *__restrict__ dp = delta + g0;
+        // 8-byte delta-pair loads when the tile is whole and its first delta 8-byte aligned
+        TIn x0[PB_NP], x1[PB_NP];
+        if (r0 + PB_TILE <= end && ((((unsigned long long)dp) & 7ull) == 0ull)) {
+            const u64 *__restrict__ vp = (const u64 *)dp;
+#pragma unroll
+            for (int k = 0; k < PB_NP; ++k) {
+                const long long g = g0 + 2 * (long long)(tid + k * PB_THREADS);
+                const u64 raw = __builtin_nontemporal_load(vp + tid + k * PB_THREADS);
+                x0[k] = TIn((g < fe ? fb_lo : fb_hi) + (u64)(u32)raw);
+                x1[k] = TIn((g + 1 < fe ? fb_lo : fb_hi) + (raw >> 32));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < PB_NP; ++k) {
+                const long long row = r0 + 2 * (long long)(tid + k * PB_THREADS);
+                const long long g = first + row;
+                x0[k] = row < end ? TIn((g < fe ? fb_lo : fb_hi) + (u64)__builtin_nontemporal_load(delta + g)) : TIn(0);
+                x1[k] = row + 1 < end ? TIn((g + 1 < fe ? fb_lo : fb_hi) + (u64)__builtin_nontemporal_load(delta + g + 1))
+                                      : TIn(0);
+            }
+        }
+)"
+               : R"(        // 16-byte row-pair loads when the tile is whole and 16-byte aligned
         TIn x0[PB_NP], x1[PB_NP];
         if (r0 + PB_TILE <= end && ((((unsigned long long)(col + r0)) & 15ull) == 0ull)) {
             const u32x4 *__restrict__ vp = (const u32x4 *)(col + r0);
@@ -3608,7 +3650,8 @@ fq_jit_pblocks(const TIn *__restrict__ col, long long n, long long B, Consts c,
                 x1[k] = row + 1 < end ? __builtin_nontemporal_load(col + row + 1) : TIn(0);
             }
         }
-#pragma unroll
+)";
+    s += R"(#pragma unroll
         for (int k = 0; k < PB_NP; ++k) {
             const long long row = r0 + 2 * (long long)(tid + k * PB_THREADS);
             const u32 live0 = row < end ? 1u : 0u, live1 = row + 1 < end ? 1u : 0u;
@@ -3929,6 +3972,11 @@ bool gen_project_source(const ProjLaunch &P, int32_t tin, int dev, Gen &g, std::
     // several columns, or a typed shape over one: the row is x0 .. x{K-1}
     const int K = P.typed ? P.n_cols : (P.n_cols > 1 ? P.n_cols : 0);
     auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    if (P.for32) {  // a module of its own: the head and fq_jit_pblocks_for32 alone
+        if (P.typed || K || tin != FQ_DT_UINT64 || !gen_project_head(P, tin, g, src)) return false;
+        src += gen_project_blocks_kernel(P, 0, true);
+        return true;
+    }
     if (!(P.typed ? gen_project_typed_head(P, src) : gen_project_head(P, tin, g, src))) return false;
     if (K) src += gen_project_bits_cols(K);
     else src += R"(
@@ -4880,11 +4928,17 @@ fq_status get_proj_kernels(int32_t col_dtype, const ProjLaunch &P, ProjKernels *
         Compiled c;
         if (!gen_project_source(P, col_dtype, dev, g, src))
             return fqc::fail(FQ_E_UNSUPPORTED, "fused projection: column/expression types outside the device path");
-        fq_status s = compile(src, dev, c, "fq_jit_pselect");
+        fq_status s = compile(src, dev, c, P.for32 ? "fq_jit_pblocks_for32" : "fq_jit_pselect");
         if (s != FQ_OK) return s;
         ProjKernels k;
         if (dev < 0) {  // validated only
             *out = k;
+            return FQ_OK;
+        }
+        if (P.for32) {  // the module holds that kernel alone
+            k.blocks = c.fn;
+            k.mod = c.mod;
+            *out = g_proj_cache.emplace(key, k).first->second;
             return FQ_OK;
         }
         k.scatter = c.fn;
@@ -5017,7 +5071,11 @@ fq_status jit_project_blocks(int32_t col_dtype, const ProjLaunch &P, int64_t blo
     int al = 1;  // PB_STAGE row pairs need 16-byte aligned outputs
     for (int j = 0; j < P.n_out; ++j) al &= ((uintptr_t)P.out[j] & 15) == 0;
     ProjArgs pa(P);
-    void **args = pa.with(&n, &B, &hc, &d_bitmap, &outs, &d_counts, &d_flags, &d_total, &d_ticket, &al);
+    const uint64_t *fbase = P.for32_base;
+    long long first = P.for32_first;
+    // fq_jit_pblocks_for32(delta, fbase, first, n, B, ...)
+    void **args = P.for32 ? pa.with(&fbase, &first, &n, &B, &hc, &d_bitmap, &outs, &d_counts, &d_flags, &d_total, &d_ticket, &al)
+                          : pa.with(&n, &B, &hc, &d_bitmap, &outs, &d_counts, &d_flags, &d_total, &d_ticket, &al);
     hipFunction_t fn = k.blocks;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);

@@ -264,6 +264,12 @@ struct ProjLaunch {
     bool typed;
     int rows;
     int group;
+    // fq_filter_project_blocks_for32 (jit_project_blocks only): col holds the
+    // per-frame 32-bit deltas of an encoded UInt64 column, for32_base its frame
+    // bases, and the n rows are [for32_first, for32_first + n) of it
+    bool for32;
+    const uint64_t *for32_base;
+    int64_t for32_first;
 };
 
 // Load geometry of a typed projection over columns of widths cdt whose widest

@@ -30,7 +30,7 @@ GPU_SYMBOLS = [
     "fq_predicate_bitmap_typed", "fq_jit_prepare_project_typed", "fq_aggregate_nullable_workspace_bytes",
     "fq_aggregate_nullable", "fq_jit_prepare_nullable", "fq_for32_frames", "fq_for32_delta_bytes",
     "fq_for32_base_bytes", "fq_for32_encode", "fq_aggregate_for32", "fq_aggregate_for32_expr",
-    "fq_jit_prepare_for32",
+    "fq_jit_prepare_for32", "fq_filter_project_blocks_for32", "fq_jit_prepare_project_for32",
 ]
 
 
@@ -93,6 +93,10 @@ _protos = {
                                             vp, vp, C.c_size_t, vp]),
     "fq_jit_prepare_for32": (C.c_int32, [C.c_int64, C.c_int64, P(abi.fq_pred), P(abi.fq_expr), C.c_uint32,
                                          P(C.c_int32)]),
+    "fq_filter_project_blocks_for32": (C.c_int32, [vp, vp, C.c_int64, C.c_int64, C.c_int64, P(abi.fq_pred),
+                                                   P(abi.fq_expr), C.c_int32, P(vp), vp, P(C.c_int64), vp, C.c_size_t,
+                                                   vp]),
+    "fq_jit_prepare_project_for32": (C.c_int32, [C.c_int64, P(abi.fq_pred), P(abi.fq_expr), C.c_int32, P(C.c_int32)]),
     "fq_arith_result_type": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, P(C.c_int32)]),
     "fq_arith": (C.c_int32, [C.c_int32, P(abi.fq_col), P(abi.fq_value), P(abi.fq_col),
                              P(abi.fq_value), P(abi.fq_col), vp, vp]),

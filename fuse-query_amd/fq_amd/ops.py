@@ -461,6 +461,48 @@ def filter_project_blocks(col, block_rows, pred, values, stream=None, out_offset
     return outs, cnt
 
 
+def filter_project_blocks_for32(enc, block_rows, pred, values, first=0, length=None, stream=None, out_offset=0):
+    """fq_filter_project_blocks_for32: filter_project_blocks over rows [first,
+    first + length) of the UInt64 column a For32Column stands for (length None:
+    up to its end), read as 4-byte deltas -> what filter_project_blocks returns
+    for the decoded window.  A bitmap predicate's rows are relative to the
+    window."""
+    require_gpu()
+    n = enc.len - int(first) if length is None else int(length)
+    n_out = len(values)
+    exprs = _project_exprs(values, abi.DT_UINT64)
+    outs = []
+    for j in range(n_out):
+        dt = exprs[j].out_dtype
+        if out_offset:
+            full = empty_column(max(n, 0) + out_offset, dt)
+            outs.append(DeviceColumn(full.buf, max(n, 0), dt, offset=8 * out_offset))
+        else:
+            outs.append(empty_column(max(n, 0), dt))
+    ptrs = (C.c_void_p * max(n_out, 1))(*[o.ptr for o in outs])
+    nb = (1 if block_rows >= n else -(-n // block_rows)) if block_rows > 0 and n > 0 else 0
+    counts = Workspace(max(8 * nb, 8))
+    ws = Workspace(lib.fq_filter_project_blocks_workspace_bytes())
+    kept = C.c_int64(0)
+    check(lib.fq_filter_project_blocks_for32(C.c_void_p(enc.delta.ptr), C.c_void_p(enc.base.ptr), int(first), n,
+                                             int(block_rows), C.byref(pred) if pred is not None else None, exprs, n_out,
+                                             ptrs, counts.ptr, C.byref(kept), ws.ptr, ws.nbytes, _stream(stream)))
+    cnt = counts.buf[:8 * nb].view(torch.int64).cpu().numpy() if nb else np.zeros(0, np.int64)
+    assert int(cnt.sum()) == kept.value
+    return outs, cnt
+
+
+def jit_prepare_project_for32(pred=None, values=(None,), block_rows=10000):
+    """Compile fq_filter_project_blocks_for32's kernel for this shape ahead of
+    time (works without a GPU: the source is then only compiled for gfx950);
+    returns True if the shape has a module."""
+    exprs = _project_exprs(values, abi.DT_UINT64)
+    out = C.c_int32(0)
+    check(lib.fq_jit_prepare_project_for32(int(block_rows), C.byref(pred) if pred is not None else None, exprs,
+                                           len(values), C.byref(out)))
+    return bool(out.value)
+
+
 def predicate_bitmap(col, pred, stream=None):
     """FilterTransform's predicate as a Boolean column (fq_predicate_bitmap)."""
     require_gpu()

@@ -530,6 +530,34 @@ fq_status fq_predicate_bitmap_columns(const fq_col *cols, int32_t n_cols, const 
 fq_status fq_jit_prepare_project_columns(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
                                          const fq_expr *values, int32_t n_out, int32_t *specialised);
 
+/* ---- Filter -> Projection block stream over a frame-of-reference copy ----
+ * fq_filter_project_blocks over rows [first, first + len) of the UInt64 column
+ * that fq_for32_encode stored as d_base / d_delta (both the encoded column's
+ * own starts; the window may begin and end anywhere in a frame, and must lie
+ * inside the encoded column): row r of the window is
+ * d_base[(first + r) / FQ_FOR32_FRAME_ROWS] + d_delta[first + r], read as 4
+ * bytes.  Geometry (blocks count from the window's first row), workspace
+ * (fq_filter_project_blocks_workspace_bytes), outputs, d_counts, *out_len,
+ * synchronisation, the error order and the error texts are
+ * fq_filter_project_blocks' over the decoded window, byte for byte; the rows of
+ * a FQ_PRED_BITMAP predicate are relative to the window.  Runs on a
+ * hipRTC-specialised kernel of its own (fq_jit_pblocks_for32): FQ_E_UNSUPPORTED
+ * with FQ_JIT_OFF or without hipRTC, and for FQ_PRED_NONE / a NULL predicate
+ * (no row dropped: nothing for this kernel to do).  FQ_E_INVALID, before any
+ * device call, for a NULL d_delta / d_base / d_out[j] / d_counts with len > 0,
+ * first < 0, len < 0, first + len past INT64_MAX, block_rows <
+ * FQ_PROJECT_MIN_BLOCK_ROWS, or a d_delta / d_base not aligned to its element
+ * (4 / 8 bytes; the plain call checks d_counts only after compiling the shape).
+ * fq_jit_prepare_project_for32 compiles that kernel ahead of the first call
+ * (*specialised = 0 with FQ_JIT_OFF or without hipRTC); without a GPU the
+ * source is compiled for gfx950 only to validate it.                         */
+fq_status fq_filter_project_blocks_for32(const uint32_t *d_delta, const uint64_t *d_base, int64_t first, int64_t len,
+                                         int64_t block_rows, const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                         void *const *d_out, int64_t *d_counts, int64_t *out_len, void *d_ws,
+                                         size_t ws_bytes, void *stream);
+fq_status fq_jit_prepare_project_for32(int64_t block_rows, const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                       int32_t *specialised);
+
 /* ---- Filter -> Projection over columns, steps, comparisons and outputs of any numeric type ----
  * (`SELECT price * discount, quantity WHERE shipdate < k and quantity < q` over
  * price Float64, discount Float32, shipdate Int32, quantity UInt8).  The twins

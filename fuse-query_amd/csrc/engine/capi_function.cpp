@@ -425,6 +425,44 @@ fq_status fq_functions_eval(fq_engine *e, fq_function *const *fs, int32_t n, con
     });
 }
 
+fq_status fq_functions_eval_nullable(fq_engine *e, fq_function *const *fs, int32_t n, const fq_block *b,
+                                     const uint64_t *const *validity, void *const *d_out, uint64_t *const *d_out_validity,
+                                     size_t cap, int64_t *d_counts, int32_t *out_dtypes, int64_t *out_len,
+                                     size_t *out_bytes) {
+    if (!e || !b || n < 1 || !fs || !validity || !d_out || !d_out_validity || !out_dtypes || !out_len || !out_bytes)
+        return fqc::fail(FQ_E_INVALID, "fq_functions_eval_nullable: bad argument");
+    for (int32_t i = 0; i < n; ++i)
+        if (!fs[i]) return fqc::fail(FQ_E_INVALID, "fq_functions_eval_nullable: NULL function");
+    *out_len = 0;
+    *out_bytes = 0;
+    if (!d_counts)
+        return fqc::fail(FQ_E_UNSUPPORTED, "fq_functions_eval_nullable: contiguous nullable projection is not built");
+    return guard([&] {
+        fq::ExecCtx ctx(device_runtime(e));
+        const fq::DataBlock blk = borrow_block(*b);
+        const int64_t rows = blk.columns.empty() ? 0 : blk.columns[0].len;
+        const size_t full = (size_t)rows * 8;  // a 64-bit output of every row
+        if (blk.sub_block_rows < FQ_PROJECT_MIN_BLOCK_ROWS)
+            throw fq::FQException(FQ_E_INVALID, "fq_functions_eval_nullable: block geometry needs block_rows >= "
+                                                "FQ_PROJECT_MIN_BLOCK_ROWS");
+        *out_bytes = full;
+        if (cap < full) throw fq::FQException(FQ_E_INVALID, "fq_functions_eval_nullable: output buffers too small");
+        std::vector<std::pair<std::string, const uint64_t *>> vb;
+        for (int32_t i = 0; i < b->n_columns; ++i) {
+            if (((uintptr_t)validity[i]) % 8)
+                throw fq::FQException(FQ_E_INVALID, "fq_functions_eval_nullable: validity bitmap " + std::to_string(i) +
+                                                        " not aligned to 8 bytes");
+            vb.emplace_back(b->names[i], validity[i]);
+        }
+        for (int32_t i = 0; i < n && i < FQ_MAX_PROJECT; ++i)
+            if (rows > 0 && !d_out[i]) throw fq::FQException(FQ_E_INVALID, "fq_functions_eval_nullable: NULL output");
+        std::vector<fq::FunctionRef> funcs;
+        for (int32_t i = 0; i < n; ++i) funcs.push_back(fs[i]->f);
+        *out_len = fq::project_nullable(blk, funcs, vb, d_out, d_out_validity, d_counts, out_dtypes, ctx);
+        ctx.sync();
+    });
+}
+
 fq_status fq_function_accumulate_result(const fq_function *f, fq_scalar *states, size_t cap, size_t *n) {
     if (!f || !n || (cap > 0 && !states)) return fqc::fail(FQ_E_INVALID, "fq_function_accumulate_result: bad argument");
     return guard([&] {

@@ -1075,6 +1075,60 @@ bool project_fused(const DataBlock &b, const std::vector<FunctionRef> &funcs, co
     return true;
 }
 
+int64_t project_nullable(const DataBlock &b, const std::vector<FunctionRef> &funcs,
+                         const std::vector<std::pair<std::string, const uint64_t *>> &validity, void *const *d_out,
+                         uint64_t *const *d_out_validity, int64_t *d_counts, int32_t *out_dtypes, ExecCtx &ctx) {
+    auto unsupported = [](const std::string &why) {
+        throw FQException(FQ_E_UNSUPPORTED,
+                          "fq_functions_eval_nullable: " + why + " (there is no unfused path over nullable columns)");
+    };
+    const std::string limits = " (more than " + std::to_string(FQ_MAX_SCAN_COLS) +
+                               " columns, a non-numeric column, or an expression outside the fused forms)";
+    if (funcs.empty() || !b.schema || b.columns.empty())
+        throw FQException(FQ_E_INVALID, "fq_functions_eval_nullable: an empty block or no functions");
+    if (funcs.size() > FQ_MAX_PROJECT)
+        unsupported("more than " + std::to_string(FQ_MAX_PROJECT) + " outputs do not fit one fused kernel");
+    if (!tree_fusion_enabled()) unsupported("the hipRTC kernels are off (FQ_JIT_OFF) or unavailable");
+    const DataSchema &s = *b.schema;
+    FusedColumns cols;
+    cols.typed = true;
+    FusedPred fp;
+    if (b.filter && !b.filter->to_pred(s, fp, &cols)) unsupported("the filter does not fuse" + limits);
+    std::vector<FusedChain> chains(funcs.size());
+    for (size_t j = 0; j < funcs.size(); ++j) {
+        if (!funcs[j]->to_chain(s, chains[j], &cols)) unsupported("function " + std::to_string(j) + " does not fuse" + limits);
+        if (!dtype_is_numeric(chains[j].out_dtype)) unsupported("function " + std::to_string(j) + " has no numeric result");
+    }
+    const int32_t n_cols = (int32_t)cols.names.size();
+    std::vector<fq_expr> exprs;
+    for (auto &fc : chains) {
+        fq_expr e = fc.expr;
+        if (n_cols > 1 && !fc.with_load(e)) unsupported("an expression does not fit a fused kernel's step budget");
+        exprs.push_back(e);
+    }
+    // the nullable lowering adds no step to the lowered programs: typed_project_fits is its dry run too
+    if (!fqk::typed_project_fits(cols.dtypes.data(), n_cols, b.filter ? fp.get() : nullptr, exprs.data(), (int32_t)exprs.size()))
+        unsupported("an expression does not fit a fused kernel's step budget");
+    fq_col ics[FQ_MAX_SCAN_COLS];
+    const uint64_t *vbs[FQ_MAX_SCAN_COLS];
+    for (int32_t j = 0; j < n_cols; ++j) {
+        const Column &c = b.column_by_name(cols.names[(size_t)j]);
+        if (!c.on_device() || !dtype_is_numeric(c.dtype)) unsupported("column " + cols.names[(size_t)j] + " is not numeric device data");
+        ics[j] = c.abi();
+        vbs[j] = nullptr;
+        for (const auto &v : validity)
+            if (v.first == cols.names[(size_t)j]) vbs[j] = v.second;
+    }
+    for (size_t j = 0; j < chains.size(); ++j) out_dtypes[j] = chains[j].out_dtype;
+    const size_t wsb = fq_filter_project_blocks_workspace_bytes();
+    auto ws = DeviceBuffer::alloc(wsb, ctx.stream());
+    int64_t kept = 0;
+    check_fq(fq_filter_project_blocks_nullable(ics, vbs, n_cols, b.sub_block_rows, b.filter ? fp.get() : nullptr, exprs.data(),
+                                               (int32_t)exprs.size(), d_out, d_out_validity, d_counts, &kept, ws->ptr, wsb,
+                                               ctx.stream()));
+    return kept;
+}
+
 // ---------------------------------------------------------------------------
 // LaunchSpan
 // ---------------------------------------------------------------------------

@@ -537,4 +537,16 @@ bool project_fused(const DataBlock &b, const std::vector<FunctionRef> &funcs, co
                    const ProjectInto *into = nullptr,
                    bool *one_kernel = nullptr);
 
+// fq_functions_eval_nullable: the same expressions (and the block's pending
+// filter) over a block whose columns carry Arrow validity bitmaps (by column
+// name; null: every row valid), as ONE fq_filter_project_blocks_nullable call
+// into the caller's buffers, in block-stream geometry.  The columns are numbered
+// as project_fused numbers them: the filter's first, then the functions'.
+// Returns the rows kept; out_dtypes[j]: output j's type.  A statement that does
+// not fuse throws FQ_E_UNSUPPORTED naming the reason: there is no unfused path
+// over nulls.
+int64_t project_nullable(const DataBlock &b, const std::vector<FunctionRef> &funcs,
+                         const std::vector<std::pair<std::string, const uint64_t *>> &validity, void *const *d_out,
+                         uint64_t *const *d_out_validity, int64_t *d_counts, int32_t *out_dtypes, ExecCtx &ctx);
+
 }  // namespace fq

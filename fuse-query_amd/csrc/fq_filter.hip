@@ -671,7 +671,9 @@ fq_status filter_project_run(int32_t col_dtype, const ProjLaunch &P, int64_t *ou
 // fq_predicate_bitmap / fq_predicate_bitmap_columns after the lowering
 fq_status predicate_bitmap_run(int32_t col_dtype, ProjLaunch &P, uint64_t *d_bitmap, uint32_t *d_flag) {
     fq_status s;
-    const std::string who = P.typed ? "fq_predicate_bitmap_typed" : P.n_cols > 1 ? "fq_predicate_bitmap_columns" : "fq_predicate_bitmap";
+    const std::string who = P.nullable ? "fq_predicate_bitmap_nullable"
+                            : P.typed  ? "fq_predicate_bitmap_typed"
+                                       : P.n_cols > 1 ? "fq_predicate_bitmap_columns" : "fq_predicate_bitmap";
     if (P.pred.kind != FQ_PRED_EXPR && P.pred.kind != FQ_PRED_TREE)
         return fqc::fail(FQ_E_INVALID, who + ": needs an FQ_PRED_EXPR or FQ_PRED_TREE predicate");
     if (!jit_project_available())
@@ -1189,6 +1191,124 @@ fq_status fq_jit_prepare_project_typed(const fq_col *cols, int32_t n_cols, int64
                                "fq_jit_prepare_project_typed", P);
     if (s != FQ_OK) return s;
     if (!jit_project_available()) return FQ_OK;  // the caller's unfused path answers
+    if ((s = jit_project_prepare(cols[0].dtype, P)) != FQ_OK) return s;
+    if (specialised) *specialised = 1;
+    return FQ_OK;
+}
+
+}  // extern "C"
+
+namespace fqk {
+namespace {
+
+// The validity arguments of the *_nullable projection entry points: the array itself non-NULL, each entry NULL or
+// 8-byte aligned.  Marks P (lowered by lower_projection_typed) nullable: every shape runs the typed kernels.
+fq_status set_nullable(const uint64_t *const *validity, const uint8_t *has_validity, int32_t n_cols, const std::string &who,
+                       ProjLaunch &P) {
+    P.nullable = true;
+    for (int j = 0; j < n_cols; ++j) {
+        if (validity && ((uintptr_t)validity[j]) % 8)
+            return fqc::fail(FQ_E_INVALID, who + ": validity bitmap " + std::to_string(j) + " not aligned to 8 bytes");
+        P.validity[j] = validity ? validity[j] : nullptr;
+        P.has_bm[j] = validity ? validity[j] != nullptr : (has_validity && has_validity[j]);
+    }
+    return FQ_OK;
+}
+
+const char *const kNullableNeedsJit = ": hipRTC unavailable or the JIT is off (there is no unfused path over nulls)";
+
+}  // namespace
+}  // namespace fqk
+
+extern "C" {
+
+fq_status fq_filter_project_blocks_nullable(const fq_col *cols, const uint64_t *const *validity, int32_t n_cols,
+                                            int64_t block_rows, const fq_pred *pred, const fq_expr *values,
+                                            int32_t n_out, void *const *d_out, uint64_t *const *d_out_validity,
+                                            int64_t *d_counts, int64_t *out_len, void *d_ws, size_t ws_bytes,
+                                            void *stream) {
+    using namespace fqk;
+    const std::string who = "fq_filter_project_blocks_nullable";
+    if (!out_len) return fqc::fail(FQ_E_INVALID, who + ": NULL out_len");
+    *out_len = 0;
+    fq_status s = check_cols_typed(cols, n_cols, true, who.c_str());
+    if (s != FQ_OK) return s;
+    if (!validity) return fqc::fail(FQ_E_INVALID, who + ": NULL validity array");
+    if (block_rows < FQ_PROJECT_MIN_BLOCK_ROWS)
+        return fqc::fail(FQ_E_INVALID, who + ": block_rows below FQ_PROJECT_MIN_BLOCK_ROWS");
+    ProjLaunch P;
+    s = lower_projection_typed(cols, n_cols, pred, values, n_out, d_out, stream, true, who.c_str(), P);
+    if (s != FQ_OK) return s;
+    if (n_out < 1) return fqc::fail(FQ_E_INVALID, who + ": no outputs");
+    if ((s = set_nullable(validity, nullptr, n_cols, who, P)) != FQ_OK) return s;
+    if (!d_out_validity) return fqc::fail(FQ_E_INVALID, who + ": NULL output validity array");
+    for (int j = 0; j < n_out; ++j) {
+        P.out_validity[j] = d_out_validity[j];
+        if (((uintptr_t)d_out_validity[j]) % 8)
+            return fqc::fail(FQ_E_INVALID, who + ": output validity bitmap " + std::to_string(j) + " not aligned to 8 bytes");
+        if (!d_out_validity[j] && project_output_nullable(P, j))
+            return fqc::fail(FQ_E_INVALID, who + ": NULL validity bitmap of output " + std::to_string(j) + ", which can hold nulls");
+    }
+    if (!jit_project_available()) return fqc::fail(FQ_E_UNSUPPORTED, who + kNullableNeedsJit);
+    if ((s = jit_project_prepare(cols[0].dtype, P)) != FQ_OK) return s;
+    const int64_t n = cols[0].len;
+    if (n == 0) return FQ_OK;
+    if (!d_counts) return fqc::fail(FQ_E_INVALID, who + ": NULL block counts");
+    if (!d_ws || ws_bytes < fq_filter_project_blocks_workspace_bytes())
+        return fqc::fail(FQ_E_INVALID, who + ": workspace too small");
+    uint64_t *const total = (uint64_t *)d_ws;
+    uint32_t *const flags = (uint32_t *)(total + 1);
+    uint32_t *const ticket = (uint32_t *)(total + 2);
+    hipStream_t st = P.stream;
+    FQ_HIP_TRY(hipMemsetAsync(d_ws, 0, fq_filter_project_blocks_workspace_bytes(), st));
+    // the kernel ORs the kept rows' bits into zeroed words
+    for (int j = 0; j < n_out; ++j)
+        if (P.out_validity[j]) FQ_HIP_TRY(hipMemsetAsync(P.out_validity[j], 0, (size_t)((n + 63) / 64) * 8, st));
+    // FQ_PRED_NONE keeps every row through the block kernel too (the module has no map kernel)
+    if ((s = jit_project_blocks(cols[0].dtype, P, block_rows, P.pred.kind == FQ_PRED_BITMAP ? P.pred.bitmap : nullptr,
+                                d_counts, flags, total, ticket)) != FQ_OK)
+        return s;
+    uint64_t local[2] = {0, 0};
+    uint64_t *const pinned = fqc::host_staging();
+    uint64_t *const host = pinned ? pinned : local;  // kept rows, flag words
+    FQ_HIP_TRY(hipMemcpyAsync(host, total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    FQ_HIP_TRY(hipStreamSynchronize(st));
+    return filter_project_blocks_result(host, out_len);
+}
+
+fq_status fq_predicate_bitmap_nullable(const fq_col *cols, const uint64_t *const *validity, int32_t n_cols,
+                                       const fq_pred *pred, uint64_t *d_bitmap, uint32_t *d_flag, void *stream) {
+    using namespace fqk;
+    const std::string who = "fq_predicate_bitmap_nullable";
+    fq_status s = check_cols_typed(cols, n_cols, true, who.c_str());
+    if (s != FQ_OK) return s;
+    if (!validity) return fqc::fail(FQ_E_INVALID, who + ": NULL validity array");
+    ProjLaunch P;
+    s = lower_projection_typed(cols, n_cols, pred, nullptr, 0, nullptr, stream, true, who.c_str(), P);
+    if (s != FQ_OK) return s;
+    if ((s = set_nullable(validity, nullptr, n_cols, who, P)) != FQ_OK) return s;
+    if (!jit_project_available()) return fqc::fail(FQ_E_UNSUPPORTED, who + kNullableNeedsJit);
+    return predicate_bitmap_run(cols[0].dtype, P, d_bitmap, d_flag);
+}
+
+fq_status fq_jit_prepare_project_nullable(const fq_col *cols, const uint8_t *has_validity, int32_t n_cols,
+                                          int64_t block_rows, const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                          int32_t *specialised) {
+    using namespace fqk;
+    const std::string who = "fq_jit_prepare_project_nullable";
+    if (specialised) *specialised = 0;
+    fq_status s = check_cols_typed(cols, n_cols, false, who.c_str());
+    if (s != FQ_OK) return s;
+    if (block_rows < FQ_PROJECT_MIN_BLOCK_ROWS)
+        return fqc::fail(FQ_E_INVALID, who + ": block_rows below FQ_PROJECT_MIN_BLOCK_ROWS (the contiguous form is not built)");
+    if (n_out < 1 || n_out > FQ_MAX_PROJECT)
+        return fqc::fail(FQ_E_INVALID, who + ": n_out must be 1.." + std::to_string(FQ_MAX_PROJECT) + ", got " +
+                                           std::to_string(n_out));
+    ProjLaunch P;
+    s = lower_projection_typed(cols, n_cols, pred, values, n_out, nullptr, nullptr, false, who.c_str(), P);
+    if (s != FQ_OK) return s;
+    (void)set_nullable(nullptr, has_validity, n_cols, who, P);
+    if (!jit_project_available()) return fqc::fail(FQ_E_UNSUPPORTED, who + kNullableNeedsJit);
     if ((s = jit_project_prepare(cols[0].dtype, P)) != FQ_OK) return s;
     if (specialised) *specialised = 1;
     return FQ_OK;

@@ -3218,6 +3218,10 @@ void pack_proj_consts(const ProjLaunch &P, HostProjConsts &hc) {
 std::string typed_proj_shape_key(const ProjLaunch &P, int dev) {
     std::string k = "PROJtyped";
     auto put = [&k](int32_t v) { k.append(reinterpret_cast<const char *>(&v), sizeof v); };
+    if (P.nullable) {  // a module of its own per set of columns that carry a bitmap
+        k += "nullable";
+        for (int j = 0; j < P.n_cols; ++j) put(P.has_bm[j] ? 1 : 0);
+    }
     put(dev);
     put(P.n_cols);
     for (int j = 0; j < P.n_cols; ++j) put(P.cdt[j]);
@@ -3760,6 +3764,53 @@ std::string gen_project_bits_cols(int K) {
            "    if (lane == 0 && flags) atomicOr(fl, flags);\n}\n";
 }
 
+// fq_jit_pbits of a nullable module (fq_predicate_bitmap_nullable): the loop
+// above, one row per lane; a wave's 64 rows of word w0 + k are bits 0..63 of
+// each bitmap's word w0 + k (one wave-uniform 8-byte load; no word at or past
+// ceil(n / 64) is read).  Bit i = the predicate is valid and true.
+std::string gen_project_bits_nullable(const ProjLaunch &P) {
+    const int K = P.n_cols;
+    auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
+    std::string vparams, vdecl, vload, vargs;
+    for (int j = 0; j < K; ++j) {
+        const std::string J = std::to_string(j);
+        if (!P.has_bm[j]) {
+            vargs += ", 1u";
+            continue;
+        }
+        vparams += "const u64 *__restrict__ vb" + J + ", ";
+        vdecl += "        u64 vw" + J + "[" + std::to_string(std::max(1, 8 / K)) + "];\n";
+        vload += "            vw" + J + "[k] = w0 + k < nwords ? vb" + J + "[w0 + k] : 0ull;\n";
+        vargs += ", (u32)((vw" + J + "[k] >> lane) & 1ull)";
+    }
+    const std::string W = std::to_string(std::max(1, 8 / K));  // 64-row words per wave per step
+    return "\nextern \"C\" __global__ void __launch_bounds__(256)\nfq_jit_pbits(" +
+           FOR("const TIn@ *__restrict__ col@, ") + vparams +
+           "long long n, Consts c, u64 *__restrict__ bm, u32 *__restrict__ fl) {\n"
+           "    const int lane = threadIdx.x & 63;\n"
+           "    const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;\n"
+           "    const long long W = ((long long)gridDim.x * 256) >> 6;\n"
+           "    const long long nwords = (n + 63) >> 6;\n"
+           "    u32 flags = 0;\n"
+           "    for (long long w0 = wave * " + W + "; w0 < nwords; w0 += W * " + W + ") {\n" +
+           FOR("        TIn@ x@[" + W + "];\n") + vdecl +
+           "#pragma unroll\n        for (int k = 0; k < " + W + "; ++k) {\n"
+           "            const long long r = (w0 + k) * 64 + lane;\n" +
+           FOR("            x@[k] = r < n ? __builtin_nontemporal_load(col@ + r) : TIn@(0);\n") + vload +
+           "        }\n        u64 mine = 0;\n"
+           "#pragma unroll\n        for (int k = 0; k < " + W + "; ++k) {\n"
+           "            const long long r = (w0 + k) * 64 + lane;\n"
+           "            const u32 live = r < n ? 1u : 0u;\n"
+           "            const bool pass = fq_pred(" + FOR("x@[k]", ", ") + vargs + ", c, flags, live) && live;\n"
+           "            const u64 word = __ballot(pass);\n"
+           "            if (lane == k) mine = word;\n"
+           "        }\n"
+           "        if (lane < " + W + " && w0 + lane < nwords) bm[w0 + lane] = mine;\n"
+           "    }\n"
+           "    flags = wave_or(flags);\n"
+           "    if (lane == 0 && flags) atomicOr(fl, flags);\n}\n";
+}
+
 // PsCtx, ps_ticket, ps_load and the head of ps_pred
 std::string gen_project_select_head_cols(int K) {
     auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
@@ -3975,6 +4026,11 @@ bool gen_project_source(const ProjLaunch &P, int32_t tin, int dev, Gen &g, std::
     if (P.for32) {  // a module of its own: the head and fq_jit_pblocks_for32 alone
         if (P.typed || K || tin != FQ_DT_UINT64 || !gen_project_head(P, tin, g, src)) return false;
         src += gen_project_blocks_kernel(P, 0, true);
+        return true;
+    }
+    if (P.nullable) {  // a module of its own: the nullable head, fq_jit_pbits and fq_jit_pblocks alone
+        if (!P.typed || !gen_project_typed_head(P, src)) return false;
+        src += gen_project_bits_nullable(P) + gen_project_typed_kernels(P);
         return true;
     }
     if (!(P.typed ? gen_project_typed_head(P, src) : gen_project_head(P, tin, g, src))) return false;
@@ -4305,6 +4361,13 @@ fq_jit_pmap(const TIn *__restrict__ col, long long n, Consts c, Outs o, int alig
 // width.  fq_jit_pmap and fq_jit_pblocks are below: a lane owns P.group
 // consecutive rows and loads its group * width bytes of each column as one
 // piece, as the typed scan does.
+//
+// P.nullable (fq_filter_project_blocks_nullable, fq_predicate_bitmap_nullable):
+// a module of its own per shape and set of columns that carry a bitmap, built
+// with TGen::nul as the nullable scan is -- fq_pred takes the rows' validity
+// bits and returns "valid and true", fq_val<j> yields the value and its
+// validity.  It holds fq_jit_pbits (gen_project_bits_nullable) and
+// fq_jit_pblocks alone: no look-back form, no map kernel.
 // ---------------------------------------------------------------------------
 const char *piece_type(int bytes) { return bytes >= 16 ? "u32x4" : bytes == 8 ? "u64" : bytes == 4 ? "u32" : bytes == 2 ? "u16" : "u8"; }
 
@@ -4314,11 +4377,15 @@ bool gen_project_typed_head(const ProjLaunch &P, std::string &src) {
     if (P.group < 1 || P.rows < P.group || P.rows % P.group || P.rows > 32) return false;
     auto FOR = [K](const std::string &t, const char *sep = "") { return for_cols(K, t, sep); };
     TGen g;
+    // a nullable module: NP, the rows' validity bits n0 .. n{K-1} after the rows' values
+    const bool nul = P.nullable;
+    g.nul = nul;
     for (int j = 0; j < K; ++j) {
         if (!tname(P.cdt[j])) return false;
         g.cdt[j] = P.cdt[j];
+        g.has_bm[j] = nul && P.has_bm[j];
     }
-    const std::string XP = FOR("TIn@ x@", ", "), XA = FOR("x@", ", ");
+    const std::string XP = FOR("TIn@ x@", ", ") + (nul ? FOR(", u32 n@") : std::string()), XA = FOR("x@", ", ");
     const bool expr_pred = P.pred.kind == FQ_PRED_EXPR || P.pred.kind == FQ_PRED_TREE;
     std::string pred_body;
     if (expr_pred && !emit_pred_typed(g, P.pred, pred_body)) return false;
@@ -4343,11 +4410,18 @@ bool gen_project_typed_head(const ProjLaunch &P, std::string &src) {
         std::string body;
         TVal cur = g.X(0);  // n_steps == 0: the chain's start column as it is
         if (P.chain[j] && !emit_prog_typed(g, body, P.vals[j], "v[" + J + "]", cur)) return false;
+        if (nul) {  // fq_val<j> yields the value and, in ok, its validity; no fq_put: the module has no map kernel
+            cur = ncast(g, body, cur, P.dtypes[j]);
+            src += std::string("typedef ") + V + " V" + J + ";\n__device__ __forceinline__ V" + J + " fq_val" + J + "(" + XP +
+                   ", const Consts &c, u32 &flags, u32 live, u32 &ok) {\n" + body + "    ok = " +
+                   (cur.v.empty() ? std::string("1u") : cur.v) + ";\n    return " + cur.e + ";\n}\n";
+            continue;
+        }
         src += std::string("typedef ") + V + " V" + J + ";\n__device__ __forceinline__ V" + J + " fq_val" + J + "(" + XP +
                ", const Consts &c, u32 &flags, u32 live) {\n" + body + "    return " + tcast(cur, P.dtypes[j]) + ";\n}\n";
         put_all += "    ((V" + J + " *)o.p[" + J + "])[pos] = fq_val" + J + "(" + XA + ", c, flags, live);\n";
     }
-    src += put_all + "}\n";
+    if (!nul) src += put_all + "}\n";
     src += R"(
 __device__ __forceinline__ u32 wave_or(u32 f) {
 #pragma unroll
@@ -4404,6 +4478,7 @@ std::string gen_project_typed_kernels(const ProjLaunch &P) {
     auto ROWS = [&FOR](const std::string &ind, const std::string &raw) {
         return FOR(ind + "TIn@ y@[PB_G];\n" + ind + "__builtin_memcpy(&y@[0], &" + raw + "[0], PB_G * sizeof(TIn@));\n");
     };
+    const size_t map_at = s.size();
     s += "#define PM_U " + std::to_string(std::max(1, 128 / (G * sum))) + "\n";
     s += "extern \"C\" __global__ void __launch_bounds__(256)\nfq_jit_pmap(" + FOR("const TIn@ *__restrict__ col@, ") +
          "long long n, Consts c, Outs o, int aligned, u32 *__restrict__ fl) {\n"
@@ -4439,7 +4514,67 @@ std::string gen_project_typed_kernels(const ProjLaunch &P) {
          "    flags = wave_or(flags);\n"
          "    if ((threadIdx.x & 63) == 0 && flags) atomicOr(fl, flags);\n}\n";
 
+    // A nullable module (fq_filter_project_blocks_nullable) has no map kernel, and its fq_jit_pblocks
+    // differs in the text that N / NFOR / VA add (all "" otherwise).  NFOR: over the columns with a
+    // bitmap vb@, # = PB_G times its number among them.  nv[k]: the validity bits of the lane's
+    // group of slab k, bit # + r = row r of that column (one register per slab whatever the
+    // bitmaps) -- a group on the grid takes them from the aligned word holding its first row's bit
+    // and, only in a block whose groups cross words (`cross`: the block starts off a multiple of
+    // PB_G rows), the next one; the element path reads one bit per row.  VA: the validity
+    // arguments of row r.
+    const bool nul = P.nullable;
+    if (nul) s.erase(map_at);
+    auto N = [nul](const std::string &t) { return nul ? t : std::string(); };
+    auto NFOR = [K, G, nul, &P](const std::string &t) {
+        std::string o;
+        for (int j = 0, nbm = 0; nul && j < K; ++j) {
+            if (!P.has_bm[j]) continue;
+            std::string u = t;
+            for (size_t p = 0; (p = u.find('@', p)) != std::string::npos;) u.replace(p, 1, std::to_string(j));
+            for (size_t p = 0; (p = u.find('#', p)) != std::string::npos;) u.replace(p, 1, std::to_string(nbm * G));
+            o += u;
+            ++nbm;
+        }
+        return o;
+    };
+    const bool any_bm = !NFOR("@").empty();
+    std::string VA;
+    for (int j = 0, nbm = 0; nul && j < K; ++j)
+        VA += P.has_bm[j] ? ", (u32)(nv[k] >> (" + std::to_string(nbm++ * G) + " + r)) & 1u" : ", 1u";
+    if (any_bm) {  // up to 4 bitmaps of up to 16 rows
+        int nbm = 0;
+        for (int j = 0; j < K; ++j) nbm += P.has_bm[j] ? 1 : 0;
+        s += "typedef " + std::string(nbm * G > 32 ? "u64" : "u32") + " NV;\n";
+    }
     s += "#define PB_ROWS " + std::to_string(P.rows) + "\n#define PB_WOUT " + std::to_string(wout) + "\n";
+    if (nul)
+        s += R"(struct OutsV { u64 *p[)" + std::to_string(FQ_MAX_PROJECT) + R"(]; };
+// bits [r0, r0 + PB_G) of the aligned word w holding bit r0 and the next word x, from bit 0 up
+__device__ __forceinline__ u32 fq_vbits(u64 w, u64 x, long long r0) {
+    const int sh = (int)(r0 & 63);
+    return (u32)((w >> sh) | ((x << 1) << (63 - sh))) & ((1u << PB_G) - 1u);
+}
+// The validity bits of a tile's kept rows, staged in LDS at bit sh + in-tile rank (sh: the bit of
+// the tile's first output row in its word), go to the output bitmap: thread t owns staged word t,
+// clears it for the next output, and ORs it into dst[t].  Block starts are no multiples of 64 in
+// general, so the first and last word of a run are shared with the previous tile of the block or
+// with another workgroup's block: every word is a device-scope atomicOr into a zeroed bitmap.
+__device__ __forceinline__ void pb_bits(u32 *__restrict__ vst, u64 *__restrict__ dst, u32 nbits, int tid) {
+    if ((u32)tid * 64u >= nbits) return;
+    const u64 w = (u64)vst[2 * tid] | ((u64)vst[2 * tid + 1] << 32);
+    vst[2 * tid] = 0u;
+    vst[2 * tid + 1] = 0u;
+    if (w) atomicOr((unsigned long long *)(dst + tid), (unsigned long long)w);
+}
+// the same for an output that is always valid: bits [sh, sh + tot) set
+__device__ __forceinline__ void pb_ones(u64 *__restrict__ dst, u32 sh, u32 tot, int tid) {
+    const u32 lo = (u32)tid * 64u, end = sh + tot;
+    if (tot == 0u || lo >= end) return;
+    u64 w = tid == 0 ? ~0ull << sh : ~0ull;
+    if (end - lo < 64u) w &= (1ull << (end - lo)) - 1ull;
+    if (w) atomicOr((unsigned long long *)(dst + tid), (unsigned long long)w);
+}
+)";
     s += R"(#define PB_THREADS 256
 #define PB_WAVES (PB_THREADS / 64)
 #define PB_TILE (PB_THREADS * PB_ROWS)
@@ -4477,15 +4612,19 @@ __device__ __forceinline__ void pb_copy(const V *__restrict__ st, u32 tot, V *__
     }
 }
 extern "C" __global__ void __launch_bounds__(PB_THREADS)
-fq_jit_pblocks()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, long long B, Consts c,
-    const u64 *__restrict__ bm, Outs o, long long *__restrict__ counts, u32 *__restrict__ fl,
+fq_jit_pblocks()" + FOR("const TIn@ *__restrict__ col@, ") + NFOR("const u64 *__restrict__ vb@, ") +
+         R"(long long n, long long B, Consts c,
+    const u64 *__restrict__ bm, Outs o, )" + N("OutsV ov, ") + R"(long long *__restrict__ counts, u32 *__restrict__ fl,
     unsigned long long *__restrict__ total, u32 *__restrict__ ticket, int al) {
     (void)al;
     __shared__ u32 off[PB_NE + 1];
     __shared__ u32x4 stage[(PB_TILE * PB_WOUT) / 16 + 2];
     __shared__ long long s_run;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long nb = (n + B - 1) / B;
+)" + N("    // the kept rows' validity bits of one output of one tile, from bit (first output row) mod 64: zero between uses\n"
+       "    __shared__ u32 vst[PB_TILE / 32 + 4];\n"
+       "    for (int q = tid; q < PB_TILE / 32 + 4; q += PB_THREADS) vst[q] = 0u;\n") +
+         R"(    const long long nb = (n + B - 1) / B;
     u64 kept = 0;  // the workgroup's kept rows
     u32 pflags = 0, vflags = 0;
     // one block per draw from the counter: the blocks in flight stay adjacent
@@ -4496,8 +4635,9 @@ fq_jit_pblocks()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, lon
         if (run >= nb) break;
         const long long end = (run + 1) * B < n ? (run + 1) * B : n;
         u64 carry = 0;  // the block's kept rows so far
-        for (long long r0 = run * B; r0 < end; r0 += PB_TILE) {
-)" + FOR("            P@ raw@[PB_NS][NP@];\n") +
+)" + (any_bm ? "        const bool cross = ((run * B) % PB_G) != 0;  // the block's groups cross bitmap words\n" : "") +
+         R"(        for (long long r0 = run * B; r0 < end; r0 += PB_TILE) {
+)" + FOR("            P@ raw@[PB_NS][NP@];\n") + (any_bm ? "            NV nv[PB_NS];\n" : "") +
          "            const bool grid = ((" + FOR("(unsigned long long)(col@ + r0) & (PB_G * sizeof(TIn@) - 1)", " | ") +
          ") == 0ull);\n"
          "#pragma unroll\n            for (int k = 0; k < PB_NS; ++k) {\n"
@@ -4505,11 +4645,22 @@ fq_jit_pblocks()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, lon
          "                if (grid && row + PB_G <= end) {\n" +
          FOR("                    _Pragma(\"unroll\") for (int q = 0; q < NP@; ++q) raw@[k][q] = "
              "__builtin_nontemporal_load((const P@ *)(col@ + row) + q);\n") +
+         // rows [row, row + PB_G) lie below end <= n: the next word, where a group reaches it, is below ceil(n / 64)
+         (any_bm ? "                    nv[k] = 0;\n" : "") +
+         NFOR("                    {\n"
+              "                        const u64 w = vb@[row >> 6];\n"
+              "                        u64 x = 0ull;\n"
+              "                        if (cross && (int)(row & 63) + PB_G > 64) x = vb@[(row >> 6) + 1];\n"
+              "                        nv[k] |= (NV)fq_vbits(w, x, row) << #;\n"
+              "                    }\n") +
          "                } else {\n" +
          FOR("                    TIn@ y@[PB_G];\n"
              "                    _Pragma(\"unroll\") for (int r = 0; r < PB_G; ++r) y@[r] = row + r < end ? "
              "__builtin_nontemporal_load(col@ + row + r) : TIn@(0);\n"
              "                    __builtin_memcpy(&raw@[k][0], &y@[0], PB_G * sizeof(TIn@));\n") +
+         (any_bm ? "                    nv[k] = 0;\n" : "") +
+         NFOR("                    _Pragma(\"unroll\") for (int r = 0; r < PB_G; ++r)\n"
+              "                        if (row + r < end) nv[k] |= (NV)((vb@[(row + r) >> 6] >> ((row + r) & 63)) & 1ull) << (# + r);\n") +
          "                }\n            }\n"
          "            u32 m[PB_NS], rk[PB_NS];  // the lane's kept rows of each slab; the rank of the first of them\n"
          "#pragma unroll\n            for (int k = 0; k < PB_NS; ++k) {\n"
@@ -4521,7 +4672,7 @@ fq_jit_pblocks()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, lon
     s += P.pred.kind == FQ_PRED_BITMAP
              ? std::string("                    const bool p = live && ((bm[(row + r) >> 6] >> ((row + r) & 63)) & 1ull);\n"
                            "                    (void)c;\n")
-             : "                    const bool p = fq_pred(" + FOR("y@[r]", ", ") + ", c, pflags, live) && live;\n";
+             : "                    const bool p = fq_pred(" + FOR("y@[r]", ", ") + VA + ", c, pflags, live) && live;\n";
     s += "                    mk |= p ? (1u << r) : 0u;\n                }\n                m[k] = mk;\n            }\n";
     for (int k = 0; k < NS; k += 2) {
         const std::string A = std::to_string(k), Bk = std::to_string(k + 1);
@@ -4545,8 +4696,40 @@ fq_jit_pblocks()" + FOR("const TIn@ *__restrict__ col@, ") + R"(long long n, lon
 #pragma unroll
             for (int k = 0; k < PB_NS; ++k) rk[k] += off[k * PB_WAVES + wave];
             const long long base = run * B + (long long)carry;
-)";
-    for (int j = 0; j < P.n_out; ++j) {
+)" + N("            const u32 vsh = (u32)(base & 63);  // the bit of output row `base` in its word\n");
+    for (int j = 0; nul && j < P.n_out; ++j) {
+        // as below, and the kept rows' validity: a lane's kept rows of a slab hold consecutive ranks, so
+        // their bits are one run of at most PB_G bits, OR-ed into the LDS bit stage at vsh + rank (two
+        // 32-bit words at the most); an output whose validity expression is empty stages nothing
+        const std::string J = std::to_string(j);
+        const bool always = !project_output_nullable(P, j);
+        s += "            {\n                V" + J + " *__restrict__ dst = (V" + J + " *)o.p[" + J + "] + base;\n"
+             "                V" + J + " *__restrict__ st = (V" + J + " *)stage + (u32)(((unsigned long long)dst & 15ull) / sizeof(V" + J + "));\n" +
+             (j ? "                __syncthreads();  // the stages are read out\n" : "") +
+             "#pragma unroll\n                for (int k = 0; k < PB_NS; ++k) {\n" + ROWS("                    ", "raw@[k]") +
+             "                    u32 vrun = 0u;\n"
+             "#pragma unroll\n                    for (int r = 0; r < PB_G; ++r)\n"
+             "                        if ((m[k] >> r) & 1u) {\n"
+             "                            const u32 q = (u32)__popc(m[k] & ((1u << r) - 1u));\n"
+             "                            u32 ok;\n"
+             "                            st[rk[k] + q] = fq_val" + J + "(" + FOR("y@[r]", ", ") + VA + ", c, vflags, 1u, ok);\n"
+             "                            vrun |= ok << q;\n"
+             "                        }\n" +
+             (always ? std::string("                    (void)vrun;\n")
+                     : "                    if (vrun && ov.p[" + J + "]) {\n"
+                       "                        const u32 p = vsh + rk[k];\n"
+                       "                        const u64 vr = (u64)vrun << (p & 31u);\n"
+                       "                        atomicOr(&vst[p >> 5], (u32)vr);\n"
+                       "                        if (vr >> 32) atomicOr(&vst[(p >> 5) + 1], (u32)(vr >> 32));\n"
+                       "                    }\n") +
+             "                }\n"
+             "                __syncthreads();\n"
+             "                pb_copy<V" + J + ">(st, tot, dst, tid);\n" +
+             (always ? "                if (ov.p[" + J + "]) pb_ones(ov.p[" + J + "] + (base >> 6), vsh, tot, tid);\n"
+                     : "                if (ov.p[" + J + "]) pb_bits(vst, ov.p[" + J + "] + (base >> 6), tot ? vsh + tot : 0u, tid);\n") +
+             "            }\n";
+    }
+    for (int j = 0; !nul && j < P.n_out; ++j) {
         const std::string J = std::to_string(j);
         s += "            {\n                V" + J + " *__restrict__ dst = (V" + J + " *)o.p[" + J + "] + base;\n"
              "                V" + J + " *__restrict__ st = (V" + J + " *)stage + (u32)(((unsigned long long)dst & 15ull) / sizeof(V" + J + "));\n" +
@@ -4655,6 +4838,19 @@ fq_status compile(const std::string &src, int dev, Compiled &out, const char *fn
 }  // namespace
 
 void jit_count_interp() { g_interp_launches += 1; }
+
+bool project_output_nullable(const ProjLaunch &P, int j) {
+    TGen g;
+    g.nul = true;
+    for (int k = 0; k < P.n_cols; ++k) {
+        g.cdt[k] = P.cdt[k];
+        g.has_bm[k] = P.has_bm[k];
+    }
+    std::string body;
+    TVal cur = g.X(0);
+    if (P.chain[j] && !emit_prog_typed(g, body, P.vals[j], "v", cur)) return true;
+    return !ncast(g, body, cur, P.dtypes[j]).v.empty();
+}
 
 namespace {
 
@@ -4928,11 +5124,18 @@ fq_status get_proj_kernels(int32_t col_dtype, const ProjLaunch &P, ProjKernels *
         Compiled c;
         if (!gen_project_source(P, col_dtype, dev, g, src))
             return fqc::fail(FQ_E_UNSUPPORTED, "fused projection: column/expression types outside the device path");
-        fq_status s = compile(src, dev, c, P.for32 ? "fq_jit_pblocks_for32" : "fq_jit_pselect");
+        fq_status s = compile(src, dev, c, P.for32 ? "fq_jit_pblocks_for32" : P.nullable ? "fq_jit_pblocks" : "fq_jit_pselect");
         if (s != FQ_OK) return s;
         ProjKernels k;
         if (dev < 0) {  // validated only
             *out = k;
+            return FQ_OK;
+        }
+        if (P.nullable) {  // the module holds the block kernel and the predicate bitmap's
+            k.blocks = c.fn;
+            k.mod = c.mod;
+            FQ_HIP_TRY(hipModuleGetFunction(&k.bits, c.mod, "fq_jit_pbits"));
+            *out = g_proj_cache.emplace(key, k).first->second;
             return FQ_OK;
         }
         if (P.for32) {  // the module holds that kernel alone
@@ -4956,13 +5159,18 @@ fq_status get_proj_kernels(int32_t col_dtype, const ProjLaunch &P, ProjKernels *
 // a *_columns call; the caller appends the rest.
 struct ProjArgs {
     const void *cols[FQ_MAX_SCAN_COLS];
-    void *v[FQ_MAX_SCAN_COLS + 12];
+    const uint64_t *vbs[FQ_MAX_SCAN_COLS];
+    void *v[2 * FQ_MAX_SCAN_COLS + 13];
     int n = 0;
     explicit ProjArgs(const ProjLaunch &P) {
         const int K = P.n_cols > 1 ? P.n_cols : 1;
         for (int j = 0; j < K; ++j) {
             cols[j] = P.n_cols > 1 ? P.cols[j] : P.col;
             v[n++] = &cols[j];
+        }
+        for (int j = 0; P.nullable && j < K; ++j) {  // a nullable module: the bitmaps follow the columns
+            vbs[j] = P.validity[j];
+            if (P.has_bm[j]) v[n++] = &vbs[j];
         }
     }
     template <typename... A>
@@ -5074,8 +5282,14 @@ fq_status jit_project_blocks(int32_t col_dtype, const ProjLaunch &P, int64_t blo
     const uint64_t *fbase = P.for32_base;
     long long first = P.for32_first;
     // fq_jit_pblocks_for32(delta, fbase, first, n, B, ...)
+    struct {
+        uint64_t *p[FQ_MAX_PROJECT];
+    } outs_v;  // a nullable module: the outputs' bitmaps follow the outputs
+    for (int j = 0; j < FQ_MAX_PROJECT; ++j) outs_v.p[j] = P.nullable && j < P.n_out ? P.out_validity[j] : nullptr;
     void **args = P.for32 ? pa.with(&fbase, &first, &n, &B, &hc, &d_bitmap, &outs, &d_counts, &d_flags, &d_total, &d_ticket, &al)
-                          : pa.with(&n, &B, &hc, &d_bitmap, &outs, &d_counts, &d_flags, &d_total, &d_ticket, &al);
+                  : P.nullable
+                      ? pa.with(&n, &B, &hc, &d_bitmap, &outs, &outs_v, &d_counts, &d_flags, &d_total, &d_ticket, &al)
+                      : pa.with(&n, &B, &hc, &d_bitmap, &outs, &d_counts, &d_flags, &d_total, &d_ticket, &al);
     hipFunction_t fn = k.blocks;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);

@@ -270,7 +270,19 @@ struct ProjLaunch {
     bool for32;
     const uint64_t *for32_base;
     int64_t for32_first;
+    // fq_filter_project_blocks_nullable / fq_predicate_bitmap_nullable (a typed
+    // launch; jit_project_blocks and jit_project_bits only): has_bm[j], column j
+    // carries an Arrow validity bitmap validity[j] (bit i = row i of cols[j]);
+    // out_validity[j]: output j's bitmap (bit p = row p of out[j]; zeroed by the
+    // caller on the stream), null only where project_output_nullable is false
+    bool nullable;
+    bool has_bm[FQ_MAX_SCAN_COLS];
+    const uint64_t *validity[FQ_MAX_SCAN_COLS];
+    uint64_t *out_validity[FQ_MAX_PROJECT];
 };
+// output j of a nullable launch can hold a null: the lowering gives its value a
+// validity expression (a column with a bitmap, or a cast that can leave its range)
+bool project_output_nullable(const ProjLaunch &P, int j);
 
 // Load geometry of a typed projection over columns of widths cdt whose widest
 // output has wout bytes.  Rows per thread per tile R: the largest power of two

@@ -31,6 +31,7 @@ GPU_SYMBOLS = [
     "fq_aggregate_nullable", "fq_jit_prepare_nullable", "fq_for32_frames", "fq_for32_delta_bytes",
     "fq_for32_base_bytes", "fq_for32_encode", "fq_aggregate_for32", "fq_aggregate_for32_expr",
     "fq_jit_prepare_for32", "fq_filter_project_blocks_for32", "fq_jit_prepare_project_for32",
+    "fq_filter_project_blocks_nullable", "fq_predicate_bitmap_nullable", "fq_jit_prepare_project_nullable",
 ]
 
 
@@ -138,6 +139,12 @@ _protos = {
     "fq_predicate_bitmap_typed": (C.c_int32, [P(abi.fq_col), C.c_int32, P(abi.fq_pred), vp, vp, vp]),
     "fq_jit_prepare_project_typed": (C.c_int32, [P(abi.fq_col), C.c_int32, C.c_int64, P(abi.fq_pred),
                                                  P(abi.fq_expr), C.c_int32, P(C.c_int32)]),
+    "fq_filter_project_blocks_nullable": (C.c_int32, [P(abi.fq_col), P(vp), C.c_int32, C.c_int64, P(abi.fq_pred),
+                                                      P(abi.fq_expr), C.c_int32, P(vp), P(vp), vp, P(C.c_int64), vp,
+                                                      C.c_size_t, vp]),
+    "fq_predicate_bitmap_nullable": (C.c_int32, [P(abi.fq_col), P(vp), C.c_int32, P(abi.fq_pred), vp, vp, vp]),
+    "fq_jit_prepare_project_nullable": (C.c_int32, [P(abi.fq_col), P(C.c_uint8), C.c_int32, C.c_int64, P(abi.fq_pred),
+                                                    P(abi.fq_expr), C.c_int32, P(C.c_int32)]),
     "fq_group_table_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "fq_group_table_init": (C.c_int32, [P(abi.fq_group_table), vp]),
     "fq_group_aggregate": (C.c_int32, [P(abi.fq_group_table), P(abi.fq_col), P(abi.fq_pred), P(abi.fq_expr),

@@ -46,6 +46,7 @@ FUNCTION_SYMBOLS = [
     "fq_function_eval", "fq_function_accumulate", "fq_function_accumulate_result", "fq_function_merge_state",
     "fq_function_merge_result", "fq_data_value_arithmetic_op", "fq_data_value_aggregate_op",
     "fq_functions_accumulate", "fq_functions_eval", "fq_functions_accumulate_nullable",
+    "fq_functions_eval_nullable",
 ]
 
 _protos = {
@@ -65,6 +66,9 @@ _protos = {
     "fq_functions_accumulate_nullable": (C.c_int32, [OPT, P(OPT), C.c_int32, P(fq_block), P(C.c_void_p)]),
     "fq_functions_eval": (C.c_int32, [OPT, P(OPT), C.c_int32, P(fq_block), P(C.c_void_p), C.c_size_t, C.c_void_p,
                                       P(C.c_int32), P(C.c_int64), P(C.c_size_t), P(C.c_int32)]),
+    "fq_functions_eval_nullable": (C.c_int32, [OPT, P(OPT), C.c_int32, P(fq_block), P(C.c_void_p), P(C.c_void_p),
+                                               P(C.c_void_p), C.c_size_t, C.c_void_p, P(C.c_int32), P(C.c_int64),
+                                               P(C.c_size_t)]),
     "fq_function_accumulate_result": (C.c_int32, [OPT, P(fq_scalar), C.c_size_t, P(C.c_size_t)]),
     "fq_function_merge_state": (C.c_int32, [OPT, P(fq_scalar), C.c_size_t]),
     "fq_function_merge_result": (C.c_int32, [OPT, P(fq_scalar)]),
@@ -308,6 +312,47 @@ class Function:
         if blocks:
             return cols, counts[:nb].cpu().numpy().astype(np.int64), bool(fused.value)
         return cols, bool(fused.value)
+
+    @staticmethod
+    def eval_all_nullable(engine, funcs, block, validity, blocks=True, fill=None, out_validity=None):
+        """eval_all over a block of nullable columns through
+        fq_functions_eval_nullable, in block-stream geometry (blocks=False passes
+        no counts: the contiguous form, which is refused).  validity: per column
+        of the block None or a UInt64 ops.DeviceColumn of Arrow validity-bitmap
+        words.  -> (columns, [UInt64 DeviceColumn of ceil(rows / 64) + 1 words per
+        output: its validity, then one sentinel word], counts).  fill: a byte the
+        buffers and bitmaps are set to first; out_validity: per output None to
+        pass a NULL bitmap."""
+        import numpy as np
+        import torch
+
+        from . import ops
+
+        _sync_torch()
+        assert len(validity) == len(block.columns)
+        n, rows = len(funcs), block.num_rows()
+        cap = max(8, rows * 8)
+        words = (rows + 63) // 64 + 1
+        outs = [torch.empty(cap, dtype=torch.uint8, device="cuda") for _ in funcs]
+        outv = [torch.empty(words * 8, dtype=torch.uint8, device="cuda") for _ in funcs]
+        if fill is not None:
+            for t in outs + outv:
+                t.fill_(int(fill) & 0xFF)
+        ptrs = (C.c_void_p * max(1, n))(*[o.data_ptr() for o in outs])
+        vptrs = (C.c_void_p * max(1, n))(*[None if out_validity is not None and out_validity[j] is None else v.data_ptr()
+                                           for j, v in enumerate(outv)])
+        arr = (OPT * max(1, n))(*[f.h for f in funcs])
+        vb = (C.c_void_p * max(1, len(validity)))(*[getattr(v, "ptr", v) for v in validity])
+        nb = -(-rows // block.block_rows) if block.block_rows > 0 else 0
+        counts = torch.zeros(max(nb, 1), dtype=torch.int64, device="cuda")
+        dts = (C.c_int32 * max(1, n))()
+        ln, nbytes = C.c_int64(0), C.c_size_t(0)
+        check(lib.fq_functions_eval_nullable(engine.h, arr, n, C.byref(block._abi()), vb, ptrs, vptrs, cap,
+                                             C.c_void_p(counts.data_ptr()) if blocks else None, dts, C.byref(ln),
+                                             C.byref(nbytes)))
+        cols = [ops.DeviceColumn(o, rows, dts[j]) for j, o in enumerate(outs)]
+        bitmaps = [ops.DeviceColumn(v, words, abi.DT_UINT64) for v in outv]
+        return cols, bitmaps, counts[:nb].cpu().numpy().astype(np.int64)
 
     def accumulate_result(self):
         n = C.c_size_t(0)

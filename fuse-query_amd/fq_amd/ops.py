@@ -680,6 +680,86 @@ def jit_prepare_project_typed(dtypes, pred=None, values=(None,), block_rows=0, l
     return bool(out.value)
 
 
+# ---- the block stream over nullable columns (Arrow validity bitmaps) ----
+def _validity_array(validity, n_cols):
+    """[None | DeviceColumn | pointer] per column -> the `validity` argument (None: a NULL array)."""
+    if validity is None:
+        return None
+    return (C.c_void_p * max(n_cols, 1))(*[getattr(v, "ptr", v) for v in validity])
+
+
+def filter_project_blocks_nullable(cols, validity, block_rows, pred, values, out_offset=0, fill=None, stream=None,
+                                   out_validity=None):
+    """fq_filter_project_blocks_nullable: filter_project_blocks_typed over
+    nullable columns.  validity: per column None or a UInt64 DeviceColumn of
+    ceil(len / 64) Arrow validity-bitmap words (bit i = row i of the column is
+    valid).  Returns ([DeviceColumn of len rows per output], [UInt64
+    DeviceColumn of ceil(len / 64) + 1 words per output: bit p = row p of the
+    output, then one sentinel word], per-block kept counts, rows kept).
+    out_offset: each output a view that many of its elements into its buffer
+    (its bitmap's bit 0 stays its row 0).  fill: a byte value the output buffers AND
+    their bitmaps are set to first (rows past a count keep it; the bitmap's words
+    are zeroed by the call, the sentinel word after them keeps it).
+    out_validity: per output None to pass a NULL bitmap (allowed only for an
+    output that cannot hold a null)."""
+    require_gpu()
+    n_out, n = len(values), cols[0].len
+    exprs = _project_exprs(values, cols[0].dtype)
+    outs, outv = [], []
+    for j in range(n_out):
+        dt = exprs[j].out_dtype
+        full = empty_column(n + out_offset, dt)
+        fullv = empty_column((n + 63) // 64 + 1, abi.DT_UINT64)
+        if fill is not None:
+            full.buf.fill_(int(fill) & 0xFF)
+            fullv.buf.fill_(int(fill) & 0xFF)
+        outs.append(DeviceColumn(full.buf, n, dt, offset=ELEM_SIZE[dt] * out_offset) if out_offset else full)
+        outv.append(fullv)
+    ptrs = (C.c_void_p * max(n_out, 1))(*[o.ptr for o in outs])
+    vptrs = (C.c_void_p * max(n_out, 1))(*[None if out_validity is not None and out_validity[j] is None else outv[j].ptr
+                                           for j in range(n_out)])
+    nb = (1 if block_rows >= n else -(-n // block_rows)) if block_rows > 0 and n > 0 else 0
+    counts = Workspace(max(8 * nb, 8))
+    ws = Workspace(lib.fq_filter_project_blocks_workspace_bytes())
+    kept = C.c_int64(0)
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    check(lib.fq_filter_project_blocks_nullable(arr, _validity_array(validity, len(cols)), len(cols), block_rows,
+                                                C.byref(pred) if pred is not None else None, exprs, n_out, ptrs, vptrs,
+                                                counts.ptr, C.byref(kept), ws.ptr, ws.nbytes, _stream(stream)))
+    cnt = counts.buf[:8 * nb].view(torch.int64).cpu().numpy() if nb else np.zeros(0, np.int64)
+    return outs, outv, cnt, kept.value
+
+
+def predicate_bitmap_nullable(cols, validity, pred, stream=None):
+    """fq_predicate_bitmap_nullable: bit i = the predicate over row i of the
+    nullable columns is valid and true, as a Boolean column."""
+    require_gpu()
+    out = empty_column(cols[0].len, abi.DT_BOOLEAN)
+    flag = Workspace(4)
+    arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+    check(lib.fq_predicate_bitmap_nullable(arr, _validity_array(validity, len(cols)), len(cols), C.byref(pred),
+                                           C.c_void_p(out.ptr), flag.ptr, _stream(stream)))
+    return out
+
+
+def jit_prepare_project_nullable(dtypes, has_validity=None, pred=None, values=(None,), block_rows=10000,
+                                 length=1 << 30, lengths=None):
+    """jit_prepare_project_typed for the *_nullable entry points (block-stream
+    geometry only): one dtype per column, and whether it will carry a validity
+    bitmap (default: none does); works without a GPU."""
+    lens = list(lengths) if lengths is not None else [int(length)] * len(dtypes)
+    arr = (abi.fq_col * max(len(dtypes), 1))(*[abi.fq_col(None, int(n), dt, 0) for dt, n in zip(dtypes, lens)])
+    hv = None
+    if has_validity is not None:
+        hv = (C.c_uint8 * max(len(dtypes), 1))(*[1 if h else 0 for h in has_validity])
+    exprs = _project_exprs(values, dtypes[0] if dtypes else 0)
+    out = C.c_int32(0)
+    check(lib.fq_jit_prepare_project_nullable(arr, hv, len(dtypes), int(block_rows),
+                                              C.byref(pred) if pred is not None else None, exprs, len(values),
+                                              C.byref(out)))
+    return bool(out.value)
+
+
 def project_compile_check(col_dtype, pred=None, values=(None,)):
     """Generate + compile the fused projection module for this shape without
     running it (no GPU needed: gfx950 code object only).  Returns the

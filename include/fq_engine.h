@@ -388,6 +388,36 @@ fq_status fq_functions_accumulate_nullable(fq_engine *e, fq_function *const *fs,
 fq_status fq_functions_eval(fq_engine *e, fq_function *const *fs, int32_t n, const fq_block *b, void *const *d_out,
                             size_t cap, int64_t *d_counts, int32_t *out_dtypes, int64_t *out_len, size_t *out_bytes,
                             int32_t *fused);
+/* The same loop body over a block of nullable columns, in block-stream
+ * geometry: one fq_filter_project_blocks_nullable call (its rules: a null
+ * predicate drops the row, an overflowing cast is a null, "Divide by zero" only
+ * where both operands are valid).  validity[i] belongs to b->columns[i] as in
+ * fq_functions_accumulate_nullable: NULL or an 8-byte aligned device bitmap,
+ * bit 0 = row 0 of the column; the array itself non-NULL.  With every entry
+ * NULL only casts make nulls: the call then has the reference's cast behaviour
+ * where fq_functions_eval fails with "cast produced nulls".  The columns are
+ * numbered as fq_functions_eval numbers them: the filter's first, then the
+ * functions'.
+ *   d_out[i]           n caller-owned device buffers of cap >= 8 x the block's
+ *                      rows bytes; output i is written at its own width
+ *                      (out_dtypes[i]), block b's kept rows at
+ *                      [b * block_rows, + d_counts[b]);
+ *   d_out_validity[i]  its validity: ceil(rows / 64) words, 8-byte aligned,
+ *                      zeroed by the call, bit p = row p of d_out[i]; NULL only
+ *                      for an output that cannot hold a null (FQ_E_INVALID);
+ *   d_counts           device int64 per block; required: d_counts == NULL is
+ *                      FQ_E_UNSUPPORTED "contiguous nullable projection is not
+ *                      built".
+ * Needs block_rows >= FQ_PROJECT_MIN_BLOCK_ROWS (FQ_E_INVALID).  *out_len: the
+ * rows kept over all blocks; *out_bytes = 8 x the block's rows.  A statement
+ * that does not fuse -- a fifth column, a ninth output, a non-numeric column, an
+ * expression past the step budget, the hipRTC kernels off -- fails with
+ * FQ_E_UNSUPPORTED and a message naming the reason: there is no unfused path
+ * over nulls.  Complete when the call returns.                              */
+fq_status fq_functions_eval_nullable(fq_engine *e, fq_function *const *fs, int32_t n, const fq_block *b,
+                                     const uint64_t *const *validity, void *const *d_out,
+                                     uint64_t *const *d_out_validity, size_t cap, int64_t *d_counts,
+                                     int32_t *out_dtypes, int64_t *out_len, size_t *out_bytes);
 /* states: the function's partial state vector (aggregates in depth order);
  * *n = its length (FQ_E_INVALID when cap is short, *n = the size needed)   */
 fq_status fq_function_accumulate_result(const fq_function *f, fq_scalar *states, size_t cap, size_t *n);

@@ -601,6 +601,78 @@ fq_status fq_predicate_bitmap_typed(const fq_col *cols, int32_t n_cols, const fq
 fq_status fq_jit_prepare_project_typed(const fq_col *cols, int32_t n_cols, int64_t block_rows, const fq_pred *pred,
                                        const fq_expr *values, int32_t n_out, int32_t *specialised);
 
+/* ---- The Filter -> Projection block stream over nullable columns (Arrow validity bitmaps) ----
+ * fq_filter_project_blocks_typed over columns that carry validity bitmaps, the
+ * form ProjectionTransform takes over an Arrow host's blocks.  `validity` is
+ * fq_aggregate_nullable's argument: the array itself non-NULL, validity[j] NULL
+ * (every row of cols[j] valid) or a device pointer, 8-byte aligned, to
+ * ceil(len / 64) u64 words whose bit i (LSB first) is 1 when row i of
+ * cols[j].data is valid (FQ_E_INVALID otherwise).  Bit 0 is row 0 of
+ * cols[j].data; bits at and past len are ignored and no word at or past
+ * ceil(len / 64) is read.  A value under a 0 bit never influences a result, a
+ * flag or an error.  The rules are arrow 2.0's, the ones fq_aggregate_nullable
+ * documents:
+ *   - a constant is valid; a step is valid iff both operands are; a cast is
+ *     valid iff its input is and the value is in range -- an out-of-range cast
+ *     is a null here, never an error: FQ_STATE_CAST_NULL is never set and
+ *     "cast produced nulls" is never returned;
+ *   - "Divide by zero": a zero divisor on a live row whose operands are both
+ *     valid, cast validity included (predicate: any row; value: a kept row);
+ *   - a comparison is null if either side is; an and / or node is null if
+ *     either side is (`true or null` is null: not Kleene logic); a row is kept
+ *     iff the predicate is valid and true.  An FQ_PRED_BITMAP predicate has no
+ *     validity of its own; FQ_PRED_NONE / a NULL predicate keeps every row.
+ * Columns, coercion checks, d_out, d_counts, block_rows >=
+ * FQ_PROJECT_MIN_BLOCK_ROWS, the workspace
+ * (fq_filter_project_blocks_workspace_bytes), *out_len and the synchronisation
+ * are fq_filter_project_blocks_typed's: block b's kept rows go, in order, to
+ * rows [b * block_rows, b * block_rows + d_counts[b]) of every output, rows past
+ * the count are untouched.
+ *
+ * d_out_validity[j] is output j's bitmap: ceil(len / 64) words, 8-byte aligned,
+ * bit p describing row p of d_out[j] -- Arrow's one offset for values and
+ * validity, so a host slices block b at b * block_rows in both.  The call
+ * zeroes these words itself, on `stream`.  Afterwards bit b * block_rows + r,
+ * r < d_counts[b], is the validity of that kept row; every other bit of the
+ * ceil(len / 64) words is 0 and no word past them is written.  The value stored
+ * under a 0 output bit is unspecified.  An entry may be NULL only when the
+ * lowering proves the output always valid -- no column with a bitmap and no
+ * integer cast reaches it (FQ_E_INVALID otherwise).  Block starts are in
+ * general no multiples of 64, so neighbouring blocks, and consecutive tiles of
+ * one block, share bitmap words: the kernel combines them with device-scope
+ * atomic ORs.
+ *
+ * Errors: a predicate "Divide by zero" on any row first, then a value's on a
+ * kept row.  FQ_E_INVALID, before any device call: a NULL `validity` or
+ * d_out_validity array, a bitmap that is not 8-byte aligned, a NULL bitmap of an
+ * output that can hold nulls, block_rows below the minimum.  These entry points
+ * always run hipRTC-specialised typed kernels, 64-bit shapes included, one
+ * module per shape and set of columns that carry a bitmap (a column without one
+ * costs no load): FQ_E_UNSUPPORTED with FQ_JIT_OFF or without hipRTC -- there
+ * is no unfused path over nulls.
+ *
+ * fq_predicate_bitmap_nullable: the predicate alone, bit i = valid and true,
+ * bits past len cleared; otherwise fq_predicate_bitmap_typed.
+ * fq_jit_prepare_project_nullable compiles the shape's module (both kernels)
+ * ahead of the first call: has_validity[j] != 0 where the call will pass a
+ * bitmap (NULL: none); without a GPU the source is compiled for gfx950 only to
+ * validate it.
+ *
+ * Not built over nulls: the contiguous form (fq_filter_project), the
+ * unfiltered map kernel (FQ_PRED_NONE runs through the block kernel), the
+ * frame-of-reference window (fq_filter_project_blocks_for32), GROUP BY, and SQL
+ * (the planner has no nullable table to query).                              */
+fq_status fq_filter_project_blocks_nullable(const fq_col *cols, const uint64_t *const *validity, int32_t n_cols,
+                                            int64_t block_rows, const fq_pred *pred, const fq_expr *values,
+                                            int32_t n_out, void *const *d_out, uint64_t *const *d_out_validity,
+                                            int64_t *d_counts, int64_t *out_len, void *d_ws, size_t ws_bytes,
+                                            void *stream);
+fq_status fq_predicate_bitmap_nullable(const fq_col *cols, const uint64_t *const *validity, int32_t n_cols,
+                                       const fq_pred *pred, uint64_t *d_bitmap, uint32_t *d_flag, void *stream);
+fq_status fq_jit_prepare_project_nullable(const fq_col *cols, const uint8_t *has_validity, int32_t n_cols,
+                                          int64_t block_rows, const fq_pred *pred, const fq_expr *values, int32_t n_out,
+                                          int32_t *specialised);
+
 /* ---- AggregateFinal state merge (host, function_aggregator.rs:106-139) ----
  * Merges `n` partial states in the given order into *out (wrapping sum,
  * summed counts/blocks, max, min, OR-ed flags).  All dtypes must match.      */

@@ -397,31 +397,49 @@ static size_t part_ws_bytes(int64_t len, int log2p, GroupPartition *X, void *ws)
 // LDS table budget of the GROUP BY launch (FQ_TUNE_GROUP_LDS_KB; tools/groupby_sweep.py)
 static int group_lds_bytes() { return (int)fqc::knob(FQ_TUNE_GROUP_LDS_KB) * 1024; }
 
-// validation + lowering shared by both aggregate entry points
-static fq_status prepare_group(const fq_group_table *t, const fq_col *col, const fq_pred *pred,
-                               const fq_expr *key_expr, const fq_expr *values, void *stream, GroupLaunch &G) {
+// validation + lowering shared by the aggregate entry points (`who` names the
+// caller in the messages).  n_cols <= 1: the one column `cols`; n_cols >= 2:
+// the checked columns of fq_group_aggregate_columns, whose key, predicate and
+// arguments name them by number.
+static fq_status prepare_group(const fq_group_table *t, const fq_col *cols, int32_t n_cols, const fq_pred *pred,
+                               const fq_expr *key_expr, const fq_expr *values, void *stream, GroupLaunch &G,
+                               const char *who = "fq_group_aggregate") {
+    const std::string W = std::string(who) + ": ";
+    const fq_col *col = cols;
     TableView v;
     fq_status s = view(t, v);
     if (s != FQ_OK) return s;
-    if (!col) return fqc::fail(FQ_E_INVALID, "fq_group_aggregate: NULL column");
-    if (col->len < 0) return fqc::fail(FQ_E_INVALID, "fq_group_aggregate: negative length");
-    if (col->len > 0 && !col->data) return fqc::fail(FQ_E_INVALID, "fq_group_aggregate: NULL column data");
+    if (!col) return fqc::fail(FQ_E_INVALID, W + "NULL column");
+    if (col->len < 0) return fqc::fail(FQ_E_INVALID, W + "negative length");
+    if (col->len > 0 && !col->data) return fqc::fail(FQ_E_INVALID, W + "NULL column data");
     if (fqc::dtype_size(col->dtype) != 8 || !fqc::dtype_is_numeric(col->dtype))
         return fqc::fail(FQ_E_UNSUPPORTED, "GROUP BY needs a 64-bit column on the device path");
-    if ((uintptr_t)col->data & 7u) return fqc::fail(FQ_E_INVALID, "fq_group_aggregate: misaligned column");
+    if ((uintptr_t)col->data & 7u) return fqc::fail(FQ_E_INVALID, W + "misaligned column");
     G = GroupLaunch{};
     G.col = col->data;
     G.n = col->len;
-    s = lower_pred(pred, col->dtype, col->len, true, G.pred);
+    if (n_cols > 1) {
+        G.n_cols = n_cols;
+        for (int j = 0; j < n_cols; ++j) {
+            G.cols[j] = cols[j].data;
+            G.cdt[j] = cols[j].dtype;
+        }
+        G.rows = group_cols_rows(n_cols);
+    }
+    auto lower = [&](const fq_expr &e, KProg &out, int32_t &dt) {
+        return n_cols > 1 ? lower_expr_cols(e, G.cdt, n_cols, out, dt) : lower_expr(e, col->dtype, out, dt);
+    };
+    s = n_cols > 1 ? lower_pred_cols(pred, G.cdt, n_cols, col->len, true, G.pred)
+                   : lower_pred(pred, col->dtype, col->len, true, G.pred);
     if (s != FQ_OK) return s;
     int32_t kdt = col->dtype;
     if (key_expr && key_expr->n_steps > 0) {
-        s = lower_expr(*key_expr, col->dtype, G.key, kdt);
+        s = lower(*key_expr, G.key, kdt);
         if (s != FQ_OK) return s;
     }
     if (kdt != t->key_dtype)
-        return fqc::fail(FQ_E_INVALID, std::string("fq_group_aggregate: key expression is ") + fqc::dtype_name(kdt) +
-                                           ", table key is " + fqc::dtype_name(t->key_dtype));
+        return fqc::fail(FQ_E_INVALID, W + "key expression is " + fqc::dtype_name(kdt) + ", table key is " +
+                                           fqc::dtype_name(t->key_dtype));
     G.key_dtype = kdt;
     G.n_aggs = t->n_aggs;
     for (int a = 0; a < t->n_aggs; ++a) {
@@ -430,12 +448,11 @@ static fq_status prepare_group(const fq_group_table *t, const fq_col *col, const
         if (t->kinds[a] == FQ_AGG_COUNT) continue;
         int32_t vdt = col->dtype;
         if (values && values[a].n_steps > 0) {
-            s = lower_expr(values[a], col->dtype, G.vals[a], vdt);
+            s = lower(values[a], G.vals[a], vdt);
             if (s != FQ_OK) return s;
             G.chain[a] = true;
         }
-        if (vdt != t->dtypes[a])
-            return fqc::fail(FQ_E_INVALID, "fq_group_aggregate: argument dtype does not match the table state");
+        if (vdt != t->dtypes[a]) return fqc::fail(FQ_E_INVALID, W + "argument dtype does not match the table state");
     }
     for (int a = 0; a < FQ_MAX_GROUP_AGGS; ++a) G.states[a] = v.states[a];
     G.keys = v.keys;
@@ -494,7 +511,7 @@ fq_status fq_group_aggregate(const fq_group_table *t, const fq_col *col, const f
                              const fq_expr *key_expr, const fq_expr *values, void *stream) {
     using namespace fqk;
     GroupLaunch G;
-    fq_status s = prepare_group(t, col, pred, key_expr, values, stream, G);
+    fq_status s = prepare_group(t, col, 1, pred, key_expr, values, stream, G);
     if (s != FQ_OK) return s;
     return jit_groupby(col->dtype, G);
 }
@@ -505,6 +522,47 @@ int64_t fq_group_dense_keys(int32_t col_dtype, const fq_expr *key_expr, int32_t 
     KProg k;
     int32_t kdt = col_dtype;
     if (lower_expr(*key_expr, col_dtype, k, kdt) != FQ_OK) return 0;
+    return group_dense_bound(k, kdt, n_aggs, group_lds_bytes());
+}
+
+fq_status fq_group_aggregate_columns(const fq_group_table *t, const fq_col *cols, int32_t n_cols,
+                                     const fq_pred *pred, const fq_expr *key_expr, const fq_expr *values,
+                                     void *stream) {
+    using namespace fqk;
+    const char *who = "fq_group_aggregate_columns";
+    fq_status s = check_cols(cols, n_cols, true, who);
+    if (s != FQ_OK) return s;
+    GroupLaunch G;
+    if (n_cols == 1) {
+        // the one-column call is fq_group_aggregate; its column references must all name column 0
+        KProg kp;
+        KPred kd;
+        int32_t dt = cols->dtype;
+        if (key_expr && key_expr->n_steps > 0 && (s = lower_expr_cols(*key_expr, &cols->dtype, 1, kp, dt)) != FQ_OK)
+            return s;
+        for (int a = 0; values && t && a < t->n_aggs && a < FQ_MAX_GROUP_AGGS; ++a)
+            if (values[a].n_steps > 0 && t->kinds[a] != FQ_AGG_COUNT &&
+                (s = lower_expr_cols(values[a], &cols->dtype, 1, kp, dt)) != FQ_OK)
+                return s;
+        if ((s = lower_pred_cols(pred, &cols->dtype, 1, cols->len, false, kd)) != FQ_OK) return s;
+        s = prepare_group(t, cols, 1, pred, key_expr, values, stream, G, who);
+        if (s != FQ_OK) return s;
+        return jit_groupby(cols->dtype, G);
+    }
+    s = prepare_group(t, cols, n_cols, pred, key_expr, values, stream, G, who);
+    if (s != FQ_OK) return s;
+    return jit_groupby_columns(G);
+}
+
+int64_t fq_group_dense_keys_columns(const int32_t *col_dtypes, int32_t n_cols, const fq_expr *key_expr,
+                                    int32_t n_aggs) {
+    using namespace fqk;
+    if (!col_dtypes || n_cols < 1 || n_cols > FQ_MAX_SCAN_COLS) return 0;
+    if (n_cols == 1) return fq_group_dense_keys(col_dtypes[0], key_expr, n_aggs);
+    if (!key_expr || key_expr->n_steps < 1 || n_aggs < 1 || n_aggs > FQ_MAX_GROUP_AGGS) return 0;
+    KProg k;
+    int32_t kdt = col_dtypes[0];
+    if (lower_expr_cols(*key_expr, col_dtypes, n_cols, k, kdt) != FQ_OK) return 0;
     return group_dense_bound(k, kdt, n_aggs, group_lds_bytes());
 }
 
@@ -523,7 +581,7 @@ fq_status fq_group_aggregate_partitioned(const fq_group_table *t, const fq_col *
     if (log2_parts < 1 || log2_parts > 8)
         return fqc::fail(FQ_E_INVALID, "fq_group_aggregate_partitioned: log2_parts must be in [1, 8]");
     GroupLaunch G;
-    fq_status s = prepare_group(t, col, pred, key_expr, values, stream, G);
+    fq_status s = prepare_group(t, col, 1, pred, key_expr, values, stream, G);
     if (s != FQ_OK) return s;
     // 4-byte rows for 8-byte integer columns the caller vouches for
     G.narrow = narrow && fqc::knob(FQ_TUNE_GROUP_NARROW) && (col->dtype == FQ_DT_UINT64 || col->dtype == FQ_DT_INT64) ? 1 : 0;

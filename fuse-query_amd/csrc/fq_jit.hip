@@ -1909,6 +1909,24 @@ std::string group_shape_key(const GroupLaunch &G, int32_t tin, int dev) {
         put(G.chain[a] ? 1 : 0);
         if (G.chain[a]) prog(G.vals[a]);
     }
+    if (G.n_cols > 1) {  // fq_jit_groupby_cols: a tag of its own, the columns' dtypes, the rows per lane, every column reference
+        k.insert(0, "GC");
+        put(G.n_cols);
+        for (int j = 0; j < G.n_cols; ++j) put(G.cdt[j]);
+        put(G.rows);
+        auto cols = [&put](const KProg &p) {
+            for (int i = 0; i < p.n; ++i) put(p.s[i].col);
+        };
+        cols(G.key);
+        for (int a = 0; a < G.n_aggs; ++a)
+            if (G.chain[a]) cols(G.vals[a]);
+        put(G.pred.rhs_col);
+        cols(G.pred.lhs);
+        for (int l = 0; l < G.pred.n_leaves; ++l) {
+            put(G.pred.leaves[l].rhs_col);
+            cols(G.pred.leaves[l].lhs);
+        }
+    }
     return k;
 }
 
@@ -2542,12 +2560,113 @@ fq_jit_groupby_bins(const PRow *__restrict__ vals, const u64 *__restrict__ order
 }
 )GP";
 
+// fq_jit_groupby_cols (fq_group_aggregate_columns over K >= 2 columns): the
+// one-column kernel's mode 0 with the same rows of every column loaded
+// together.  A tile is GROWS * BT rows, row k * BT + tid of it in lane tid
+// (8-byte non-temporal loads: the columns need share no 16-byte phase, so
+// there is no head), GROWS = 4 rows per lane for two columns and 2 for three
+// and four, so that a tile and the next tile's loads in flight stay within the
+// one-column kernel's 128 bytes per lane.  The rows after the last whole tile
+// go one at a time.  No clustered layout (mode 1) and no partitioned variant.
+std::string gen_groupby_cols_kernel(int K) {
+    // FOR("text with @ for the column number") -> the text once per column
+    auto FOR = [K](const std::string &t, const char *sep = "") {
+        std::string o;
+        for (int j = 0; j < K; ++j) {
+            std::string u = t;
+            for (size_t p = 0; (p = u.find('@', p)) != std::string::npos;) u.replace(p, 1, std::to_string(j));
+            o += (j ? sep : "") + u;
+        }
+        return o;
+    };
+    std::string s = "\nextern \"C\" __global__ void __launch_bounds__(BT)\nfq_jit_groupby_cols(" +
+                    FOR("const TIn@ *__restrict__ col@, ") +
+                    "long long n, const u64 *__restrict__ bitmap,\n                    Consts c, Tab t) {\n";
+    s += R"(    __shared__ u64 s_keys[S];
+    __shared__ u64 s_st[NA][S];
+    __shared__ int s_bypass[2];  // [0] bypass flag, [1] slots claimed
+    fq_lds_reset(s_keys, s_st, s_bypass);
+    __syncthreads();
+    // this workgroup's replica of the HBM states
+    Tab tr = t;
+    const long long roff = (long long)(blockIdx.x & t.rmask) * (t.mask + 2);
+    for (int a = 0; a < NA; ++a) tr.st[a] += roff;
+    // key partitions of later launches into one table, as in fq_jit_groupby
+    const u32 seen = __hip_atomic_load(&t.hdr[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const u32 saturated = __hip_atomic_load(&t.hdr[5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    u32 P = 1;
+    if (!DENSE && saturated && seen > (u32)(S * 3 / 4))
+        while (P <= PMAX && P * (u32)(S / 2) < seen) P <<= 1;
+    if (P > PMAX || gridDim.x % P) P = 1;
+    const u32 part = blockIdx.x & (P - 1);
+    const long long RG = gridDim.x / P, rb = blockIdx.x / P;
+    u32 flags = 0;
+    const long long tile_rows = (long long)GROWS * BT;
+    const long long ntiles = n / tile_rows;
+#if GCHUNK
+    const long long per = (ntiles + RG - 1) / RG, t_lo = rb * per, t_hi = t_lo + per < ntiles ? t_lo + per : ntiles;
+    const long long t_step = 1;
+#else
+    const long long t_lo = rb, t_hi = ntiles, t_step = RG;
+#endif
+)";
+    s += FOR("    TIn@ nxt@[GROWS];\n");
+    s += "    auto gload = [&](long long tile) {\n"
+         "        const long long b = tile * tile_rows + threadIdx.x;\n"
+         "#pragma unroll\n        for (int k = 0; k < GROWS; ++k) {\n";
+    s += FOR("            nxt@[k] = __builtin_nontemporal_load(col@ + b + (long long)k * BT);\n");
+    s += "        }\n    };\n"
+         "    if (t_lo < t_hi) gload(t_lo);\n"
+         "    for (long long tt = t_lo; tt < t_hi; tt += t_step) {\n";
+    s += FOR("        TIn@ raw@[GROWS];\n");
+    s += "#pragma unroll\n        for (int k = 0; k < GROWS; ++k) { " + FOR("raw@[k] = nxt@[k]; ") + "}\n"
+         "        // the next tile's loads in flight while this tile goes through the table\n"
+         "        const long long tn = tt + t_step;\n"
+         "        if (tn < t_hi) gload(tn);\n"
+         "        Row r[GROWS];\n"
+         "#pragma unroll\n        for (int k = 0; k < GROWS; ++k) {\n"
+         "            fq_prep(" + FOR("raw@[k]", ", ") + ", tt * tile_rows + threadIdx.x + (long long)k * BT, c, bitmap, flags, r[k]);\n"
+         "            if (P > 1 && part_of(r[k].k, P) != part) r[k].pass = 0;\n"
+         "        }\n"
+         "        u32 cnt[GROWS];\n"
+         "#if GROWS > 1\n        fq_runs(r, cnt);\n#else\n        cnt[0] = r[0].pass;\n#endif\n"
+         "        u64 cur[GROWS];\n"
+         "#pragma unroll\n        for (int j = 0; j < GROWS; ++j) cur[j] = fq_first(r[j], s_keys);\n"
+         "#pragma unroll\n        for (int j = 0; j < GROWS; ++j) fq_commit_lane(r[j], cur[j], tr, s_keys, s_st, s_bypass, (u64)cnt[j]);\n"
+         "    }\n"
+         "    for (long long i = ntiles * tile_rows + rb * BT + threadIdx.x; i < n; i += RG * BT)\n"
+         "        fq_row(" + FOR("col@[i]", ", ") + ", i, c, tr, bitmap, s_keys, s_st, flags, s_bypass, P, part);\n"
+         "    if (flags) atomicOr(&t.hdr[0], flags);\n"
+         "    __syncthreads();\n"
+         "    if (threadIdx.x == 0 && s_bypass[0]) atomicOr(&t.hdr[5], 1u);\n"
+         "    fq_flush(tr, s_keys, s_st);\n}\n";
+    return s;
+}
+
 bool gen_groupby_source(const GroupLaunch &G, int32_t tin, Gen &g, std::string &src, bool cluster = true) {
     const char *TIn = ctype(tin);
     if (!TIn || (G.key_dtype != FQ_DT_UINT64 && G.key_dtype != FQ_DT_INT64)) return false;
     if (G.n_aggs < 1 || G.n_aggs > FQ_MAX_GROUP_AGGS) return false;
     const int NA = G.n_aggs;
     const int S = lds_slots(NA, G.lds_bytes);
+    // fq_group_aggregate_columns over K >= 2 columns: the per-row functions take
+    // x0 .. x{K-1}, each of its column's type (XP in their signatures, XA in
+    // the calls), and the module ends in fq_jit_groupby_cols alone
+    const int K = G.n_cols > 1 ? G.n_cols : 1;
+    std::string XP = "TIn x", XA = "x";
+    if (K > 1) {
+        if (K > FQ_MAX_SCAN_COLS || G.rows < 1 || G.rows > 8) return false;
+        g.n_cols = K;
+        XP.clear();
+        XA.clear();
+        for (int j = 0; j < K; ++j) {
+            if (!ctype(G.cdt[j])) return false;
+            g.cdt[j] = G.cdt[j];
+            const std::string J = std::to_string(j);
+            XP += (j ? ", TIn" : "TIn") + J + " x" + J;
+            XA += (j ? ", x" : "x") + J;
+        }
+    }
     src = kCommon;
     for (int a = 0; a < NA; ++a) {
         if (G.dtypes[a] == FQ_DT_FLOAT64 && (G.kinds[a] == FQ_AGG_MAX || G.kinds[a] == FQ_AGG_MIN)) {
@@ -2556,7 +2675,12 @@ bool gen_groupby_source(const GroupLaunch &G, int32_t tin, Gen &g, std::string &
             break;
         }
     }
-    src += "typedef " + std::string(TIn) + " TIn;\n";
+    if (K > 1) {
+        for (int j = 0; j < K; ++j) src += "typedef " + std::string(ctype(G.cdt[j])) + " TIn" + std::to_string(j) + ";\n";
+        src += "#define GROWS " + std::to_string(G.rows) + "\n";
+    } else {
+        src += "typedef " + std::string(TIn) + " TIn;\n";
+    }
     src += "struct Step { u64 c, m, s; };\nstruct Consts { u64 rhs; Step p[" + std::to_string(kSteps) + "], k[" +
            std::to_string(kSteps) + "], v[" + std::to_string(FQ_MAX_GROUP_AGGS) + "][" + std::to_string(kSteps) +
            "]; u64 rl[" + std::to_string(FQ_MAX_PRED_LEAVES) + "]; Step pl[" + std::to_string(FQ_MAX_PRED_LEAVES) +
@@ -2686,10 +2810,10 @@ __device__ long long ginsert(const Tab &t, u64 k) {
     } else {
         body = "    return true;\n";
     }
-    src += "__device__ __forceinline__ bool fq_pred(TIn x, const Consts &c, u32 &flags, u32 live) {\n" + body + "}\n";
+    src += "__device__ __forceinline__ bool fq_pred(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n" + body + "}\n";
     body.clear();
     emit_value_body(g, G.key.n ? &G.key : nullptr, tin, G.key_dtype, "k", "u64", body);
-    src += "__device__ __forceinline__ u64 fq_key(TIn x, const Consts &c, u32 &flags, u32 live) {\n" + body + "}\n";
+    src += "__device__ __forceinline__ u64 fq_key(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n" + body + "}\n";
     for (int a = 0; a < NA; ++a) {
         if (G.kinds[a] == FQ_AGG_COUNT) continue;
         const char *V = ctype(G.dtypes[a]);
@@ -2698,7 +2822,7 @@ __device__ long long ginsert(const Tab &t, u64 k) {
         emit_value_body(g, G.chain[a] ? &G.vals[a] : nullptr, tin, G.dtypes[a],
                         ("v[" + std::to_string(a) + "]").c_str(), V, body);
         src += std::string("__device__ __forceinline__ ") + V + " fq_val" + std::to_string(a) +
-               "(TIn x, const Consts &c, u32 &flags, u32 live) {\n" + body + "}\n";
+               "(" + XP + ", const Consts &c, u32 &flags, u32 live) {\n" + body + "}\n";
     }
     // identity of each state (fq_groupby.hip initialises the HBM table the same way)
     auto identity = [](int32_t kind, int32_t dt) -> std::string {
@@ -2715,22 +2839,22 @@ __device__ long long ginsert(const Tab &t, u64 k) {
     for (int a = 0; a < NA; ++a)
         if (G.kinds[a] != FQ_AGG_COUNT) row += std::string(" ") + ctype(G.dtypes[a]) + " v" + std::to_string(a) + ";";
     row += " };\n";
-    row += "__device__ __forceinline__ void fq_prep(TIn x, long long idx, const Consts &c,\n"
+    row += "__device__ __forceinline__ void fq_prep(" + XP + ", long long idx, const Consts &c,\n"
            "    const u64 *__restrict__ bitmap, u32 &flags, Row &r) {\n    r.pass = 1u;\n";
     if (G.pred.kind == FQ_PRED_EXPR || G.pred.kind == FQ_PRED_TREE)
-        row += "    r.pass = fq_pred(x, c, flags, 1u) ? 1u : 0u;\n";
+        row += "    r.pass = fq_pred(" + XA + ", c, flags, 1u) ? 1u : 0u;\n";
     else if (G.pred.kind == FQ_PRED_BITMAP) row += "    r.pass = (u32)((bitmap[idx >> 6] >> (idx & 63)) & 1ull);\n";
-    row += "    (void)idx; (void)bitmap;\n    r.k = fq_key(x, c, flags, r.pass);\n";
+    row += "    (void)idx; (void)bitmap;\n    r.k = fq_key(" + XA + ", c, flags, r.pass);\n";
     for (int a = 0; a < NA; ++a)
         if (G.kinds[a] != FQ_AGG_COUNT)
-            row += "    r.v" + std::to_string(a) + " = fq_val" + std::to_string(a) + "(x, c, flags, r.pass);\n";
+            row += "    r.v" + std::to_string(a) + " = fq_val" + std::to_string(a) + "(" + XA + ", c, flags, r.pass);\n";
     row += "#if DENSE\n    r.h = (int)r.k;\n#else\n    r.h = (int)(lds_hash(r.k) & (u32)(S - 1));\n#endif\n}\n";
     // rows of the partitioned buffer already passed the predicate
-    row += "__device__ __forceinline__ void fq_prep_all(TIn x, u32 live, const Consts &c, u32 &flags, Row &r) {\n"
-           "    r.pass = live;\n    r.k = fq_key(x, c, flags, live);\n";
+    row += "__device__ __forceinline__ void fq_prep_all(" + XP + ", u32 live, const Consts &c, u32 &flags, Row &r) {\n"
+           "    r.pass = live;\n    r.k = fq_key(" + XA + ", c, flags, live);\n";
     for (int a = 0; a < NA; ++a)
         if (G.kinds[a] != FQ_AGG_COUNT)
-            row += "    r.v" + std::to_string(a) + " = fq_val" + std::to_string(a) + "(x, c, flags, live);\n";
+            row += "    r.v" + std::to_string(a) + " = fq_val" + std::to_string(a) + "(" + XA + ", c, flags, live);\n";
     row += "#if DENSE\n    r.h = (int)r.k;\n#else\n    r.h = (int)(lds_hash(r.k) & (u32)(S - 1));\n#endif\n}\n";
     row += "__device__ __forceinline__ u64 fq_first(const Row &r, const u64 *s_keys) {\n"
            "#if DENSE\n    (void)r; (void)s_keys;\n    return EMPTY;\n#else\n"
@@ -2885,10 +3009,10 @@ template <int N> __device__ __forceinline__ void fq_wave_runs(Row (&r)[N], u32 (
     }
     row += "        if (lane == l0) {\n            cnt[j] = tot;\n        } else if (in) {\n            cnt[j] = 0;\n"
            "            r[j].pass = 0;\n        }\n        }\n    }\n}\n";
-    row += "__device__ __forceinline__ void fq_row(TIn x, long long idx, const Consts &c, const Tab &t,\n"
+    row += "__device__ __forceinline__ void fq_row(" + XP + ", long long idx, const Consts &c, const Tab &t,\n"
            "    const u64 *__restrict__ bitmap, u64 *s_keys, u64 (*s_st)[S], u32 &flags, int *s_bypass, u32 P,\n"
            "    u32 part) {\n"
-           "    Row r;\n    fq_prep(x, idx, c, bitmap, flags, r);\n"
+           "    Row r;\n    fq_prep(" + XA + ", idx, c, bitmap, flags, r);\n"
            "    if (P > 1 && part_of(r.k, P) != part) r.pass = 0;\n"
            "    fq_commit(r, fq_first(r, s_keys), t, s_keys, s_st, s_bypass);\n}\n";
     src += row;
@@ -2932,6 +3056,10 @@ __device__ __forceinline__ void fq_flush(const Tab &tr, const u64 *s_keys, u64 (
     }
     src += "    }\n}\n";
 
+    if (K > 1) {
+        src += gen_groupby_cols_kernel(K);
+        return true;
+    }
     // kernel
     src += R"(
 extern "C" __global__ void __launch_bounds__(BT)
@@ -5066,6 +5194,95 @@ fq_status jit_groupby(int32_t col_dtype, const GroupLaunch &G) {
     const uint64_t *bitmap = G.pred.bitmap;
     void *args[] = {&col, &n, &head, &bitmap, &hc, &tab};
     FQ_HIP_TRY(hipModuleLaunchKernel(f.agg, (unsigned)G.grid, 1, 1, (unsigned)G.threads, 1, 1, 0, G.stream, args, nullptr));
+    g_jit_launches += 1;
+    return FQ_OK;
+}
+
+namespace {
+
+// fq_jit_groupby_cols of one shape: the kernel and the rows per lane it was
+// compiled with (G.rows, halved while the shape needs scratch)
+struct GroupColsFn {
+    hipFunction_t agg = nullptr;
+    int rows = 0;
+};
+std::unordered_map<std::string, GroupColsFn> g_group_cols_cache;
+
+fq_status get_group_cols_fn(const GroupLaunch &G, GroupColsFn *out) {
+    fq_status err;
+    if (!load_rtc(FQ_JIT_ALWAYS, &err)) return err;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        dev = -1;
+    }
+    const std::string key = group_shape_key(G, G.cdt[0], dev);
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_group_cols_cache.find(key);
+    if (it == g_group_cols_cache.end()) {
+        GroupLaunch H = G;
+        Compiled c;
+        for (;;) {
+            Gen g;
+            std::string src;
+            if (!gen_groupby_source(H, H.cdt[0], g, src))
+                return fqc::fail(FQ_E_UNSUPPORTED, "GROUP BY: key/aggregate types outside the device path");
+            c = Compiled{};
+            fq_status s = compile(src, dev, c, "fq_jit_groupby_cols");
+            if (s != FQ_OK) return s;
+            int scratch = 0;
+            if (dev < 0 || hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, c.fn) != hipSuccess ||
+                scratch <= 0)
+                break;
+            // register spills: fewer rows per lane for this shape, never scratch
+            (void)hipModuleUnload(c.mod);
+            if (H.rows == 1)
+                return fqc::fail(FQ_E_INTERNAL, "fq_group_aggregate_columns: the kernel needs scratch memory at one row per lane");
+            H.rows /= 2;
+        }
+        (void)hipGetLastError();
+        if (dev < 0) {  // validated only
+            *out = GroupColsFn{};
+            return FQ_OK;
+        }
+        GroupColsFn f;
+        f.agg = c.fn;
+        f.rows = H.rows;
+        it = g_group_cols_cache.emplace(key, f).first;
+    }
+    *out = it->second;
+    return FQ_OK;
+}
+
+}  // namespace
+
+fq_status jit_groupby_columns(const GroupLaunch &G) {
+    GroupColsFn f;
+    fq_status s = get_group_cols_fn(G, &f);
+    if (s != FQ_OK || !f.agg || G.n == 0) return s;
+    HostGroupConsts hc;
+    pack_group_consts(G, hc);
+    GroupTab tab = group_tab(G);
+    // one workgroup per tile of f.rows rows per lane, at most CUs x FQ_TUNE_GROUP_WG_PER_CU
+    const int64_t tile = (int64_t)f.rows * G.threads;
+    int64_t grid = (G.n + tile - 1) / tile;
+    const int64_t cap = (int64_t)fqc::device_cu_count() * fqc::knob(FQ_TUNE_GROUP_WG_PER_CU);
+    if (grid > cap) grid = cap;
+    if (grid < 1) grid = 1;
+    const void *cols[FQ_MAX_SCAN_COLS];
+    void *args[FQ_MAX_SCAN_COLS + 4];
+    int na = 0;
+    for (int j = 0; j < G.n_cols; ++j) {
+        cols[j] = G.cols[j];
+        args[na++] = &cols[j];
+    }
+    long long n = G.n;
+    const uint64_t *bitmap = G.pred.bitmap;
+    args[na++] = &n;
+    args[na++] = &bitmap;
+    args[na++] = &hc;
+    args[na++] = &tab;
+    FQ_HIP_TRY(hipModuleLaunchKernel(f.agg, (unsigned)grid, 1, 1, (unsigned)G.threads, 1, 1, 0, G.stream, args, nullptr));
     g_jit_launches += 1;
     return FQ_OK;
 }

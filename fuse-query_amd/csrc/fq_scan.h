@@ -198,7 +198,20 @@ struct GroupLaunch {
                     // key below d <= P * S: `% d`), else bins by the key's hash
     int grid;
     hipStream_t stream;
+    // fq_group_aggregate_columns with more than one column (else n_cols == 0):
+    // the columns and their dtypes; key, predicate and arguments name them by
+    // number.  `rows`: rows per lane per tile of rows * threads rows (see
+    // group_cols_rows); the launch takes its grid from them.
+    int n_cols;
+    const void *cols[FQ_MAX_SCAN_COLS];
+    int32_t cdt[FQ_MAX_SCAN_COLS];
+    int rows;
 };
+
+// Rows per lane per tile of the GROUP BY kernel over K >= 2 columns: a tile and
+// the next tile's loads are 2 x K x rows x 8 <= 128 bytes per lane, the budget
+// of the one-column kernel's nxt[8] + raw[8]
+constexpr int group_cols_rows(int n_cols) { return n_cols <= 2 ? 4 : 2; }
 
 // Keys of a dense GROUP BY key (a UInt64 key ending in `% d`, d <= the LDS
 // slots for n_aggs states in lds_bytes): d, else 0 (fq_jit.hip)
@@ -210,6 +223,11 @@ int group_lds_slots(int n_aggs, int lds_bytes);
 
 // Launches the hipRTC-specialised group-by kernel for G.
 fq_status jit_groupby(int32_t col_dtype, const GroupLaunch &G);
+// The same over G.n_cols >= 2 columns (fq_jit_groupby_cols): a module and a
+// cache entry of its own, the grid from the rows per lane the shape compiled
+// with.  Nothing is launched for n == 0 or without a device (the shape is then
+// compiled for gfx950 only).
+fq_status jit_groupby_columns(const GroupLaunch &G);
 
 // The partitioned (high-cardinality) path of fq_group_aggregate_partitioned:
 // partition into block chains -> blocks grouped by bin -> per-bin

@@ -32,6 +32,7 @@ GPU_SYMBOLS = [
     "fq_for32_base_bytes", "fq_for32_encode", "fq_aggregate_for32", "fq_aggregate_for32_expr",
     "fq_jit_prepare_for32", "fq_filter_project_blocks_for32", "fq_jit_prepare_project_for32",
     "fq_filter_project_blocks_nullable", "fq_predicate_bitmap_nullable", "fq_jit_prepare_project_nullable",
+    "fq_group_aggregate_columns", "fq_group_dense_keys_columns",
 ]
 
 
@@ -153,6 +154,9 @@ _protos = {
     "fq_group_dense_keys": (C.c_int64, [C.c_int32, P(abi.fq_expr), C.c_int32]),
     "fq_group_aggregate_partitioned": (C.c_int32, [P(abi.fq_group_table), P(abi.fq_col), P(abi.fq_pred),
                                                    P(abi.fq_expr), P(abi.fq_expr), C.c_int32, vp, C.c_size_t, vp]),
+    "fq_group_aggregate_columns": (C.c_int32, [P(abi.fq_group_table), P(abi.fq_col), C.c_int32, P(abi.fq_pred),
+                                               P(abi.fq_expr), P(abi.fq_expr), vp]),
+    "fq_group_dense_keys_columns": (C.c_int64, [P(C.c_int32), C.c_int32, P(abi.fq_expr), C.c_int32]),
     "fq_group_table_count": (C.c_int32, [P(abi.fq_group_table), P(C.c_int64), vp]),
     "fq_group_table_extract": (C.c_int32, [P(abi.fq_group_table), vp, P(C.c_void_p), C.c_int64, P(C.c_int64),
                                            vp]),

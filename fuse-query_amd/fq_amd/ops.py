@@ -896,6 +896,19 @@ class GroupTable:
                                                  ws.nbytes, _stream(stream)))
         self._ws = ws  # alive until the next call (the launch is asynchronous)
 
+    def aggregate_columns(self, cols, pred=None, key=None, values=None, stream=None):
+        """fq_group_aggregate_columns over a list of DeviceColumns of one block
+        (expr.chain_columns / predicate_columns / pred_tree_columns number them
+        by position; key None = column 0, values[i] None = column 0)."""
+        arr = (abi.fq_col * max(len(cols), 1))(*[c.col() for c in cols])
+        vals = (abi.fq_expr * abi.MAX_GROUP_AGGS)()
+        for i, v in enumerate(values or []):
+            if v is not None:
+                vals[i] = v
+        p = C.byref(pred) if pred is not None else None
+        k = C.byref(key) if key is not None else None
+        check(lib.fq_group_aggregate_columns(C.byref(self.desc), arr, len(cols), p, k, vals, _stream(stream)))
+
     def merge(self, keys, states, stream=None):
         """fq_group_table_merge: host uint64 keys[n] and per-aggregate uint64
         states[n] (state bits) folded into this table."""
@@ -955,6 +968,40 @@ def group_dense_keys(col_dtype, key, n_aggs):
     """fq_group_dense_keys: d when the key over a column of col_dtype ends in `% d` and d fits the GROUP BY
     kernel's LDS table for n_aggs states (the table is then indexed by the key itself), else 0."""
     return int(lib.fq_group_dense_keys(col_dtype, C.byref(key) if key is not None else None, n_aggs))
+
+
+def group_compile_check_columns(col_dtypes, aggs, key=None, values=None, pred=None, key_dtype=abi.DT_UINT64,
+                                lengths=None, ptrs=None):
+    """group_compile_check for fq_group_aggregate_columns: a zero-length call
+    over columns of col_dtypes generates and compiles the shape's kernel for
+    gfx950 (no GPU needed).  lengths / ptrs: per-column len and data address,
+    for the argument checks (nothing is read)."""
+    d = abi.fq_group_table()
+    d.d_mem = 0x1000  # never dereferenced for a zero-length column
+    d.capacity = 64
+    d.key_dtype = key_dtype
+    d.n_aggs = len(aggs)
+    for i, (k, dt) in enumerate(aggs):
+        d.kinds[i] = k
+        d.dtypes[i] = dt
+    lens = list(lengths) if lengths is not None else [0] * len(col_dtypes)
+    addr = list(ptrs) if ptrs is not None else [None] * len(col_dtypes)
+    arr = (abi.fq_col * max(len(col_dtypes), 1))(*[abi.fq_col(a, int(n), dt, 0)
+                                                   for a, n, dt in zip(addr, lens, col_dtypes)])
+    vals = (abi.fq_expr * abi.MAX_GROUP_AGGS)()
+    for i, v in enumerate(values or []):
+        if v is not None:
+            vals[i] = v
+    p = C.byref(pred) if pred is not None else None
+    k = C.byref(key) if key is not None else None
+    check(lib.fq_group_aggregate_columns(C.byref(d), arr, len(col_dtypes), p, k, vals, None))
+
+
+def group_dense_keys_columns(col_dtypes, key, n_aggs):
+    """fq_group_dense_keys_columns: group_dense_keys for a key over columns of col_dtypes."""
+    arr = (C.c_int32 * max(len(col_dtypes), 1))(*col_dtypes)
+    return int(lib.fq_group_dense_keys_columns(arr, len(col_dtypes), C.byref(key) if key is not None else None,
+                                               n_aggs))
 
 
 def tune_set(name, value):

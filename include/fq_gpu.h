@@ -820,6 +820,29 @@ fq_status fq_group_aggregate_partitioned(const fq_group_table *t, const fq_col *
  * states, the kernel indexes that table by the key itself (no hashing, never
  * saturated) and the query has at most d groups: returns d, else 0. */
 int64_t fq_group_dense_keys(int32_t col_dtype, const fq_expr *key_expr, int32_t n_aggs);
+/* fq_group_aggregate over the same rows of 1..FQ_MAX_SCAN_COLS columns of one
+ * block (`sum(b) ... GROUP BY a`): cols[j] are UInt64 / Int64 / Float64 columns
+ * of equal len, 8-byte aligned; they need share no 16-byte phase.  The key,
+ * the predicate and every argument name the columns as fq_aggregate_columns
+ * documents: a step's `bits` with FQ_OPERAND_COLUMN, FQ_OP_LOAD as the first
+ * step, FQ_OP_PUSH with a column number, `rhs_bits` of a comparison against a
+ * column.  key_expr NULL or without steps is column 0, and so is an argument
+ * without steps; any other column is a one-step FQ_OP_LOAD.  The key's result
+ * type must be t->key_dtype (so a Float64 column 0 needs a key expression over
+ * an integer column) and argument a's type t->dtypes[a].  FQ_PRED_BITMAP is
+ * indexed by row.  The table, its results and its errors (at count / extract,
+ * for kept rows only) are fq_group_aggregate's, and launches of either call,
+ * of the partitioned variant and fq_group_table_merge may fill one table in
+ * any order.  There is no partitioned variant over several columns: keys that
+ * outgrow the LDS table go to the HBM table.  n_cols == 1 is
+ * fq_group_aggregate itself (same kernels).  Asynchronous. */
+fq_status fq_group_aggregate_columns(const fq_group_table *t, const fq_col *cols, int32_t n_cols,
+                                     const fq_pred *pred, const fq_expr *key_expr, const fq_expr *values,
+                                     void *stream);
+/* fq_group_dense_keys for a key expression over n_cols columns of col_dtypes
+ * (one dtype: fq_group_dense_keys of it). */
+int64_t fq_group_dense_keys_columns(const int32_t *col_dtypes, int32_t n_cols, const fq_expr *key_expr,
+                                    int32_t n_aggs);
 /* Number of groups (synchronises stream); FQ_E_TABLE_FULL if any insert
  * found no free slot, FQ_E_DIVIDE_BY_ZERO / FQ_E_UNSUPPORTED for the flags
  * fq_aggregate reports. */
